@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the ASW hot path on MI355X (contract in the task prompt).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the line: the headline figure, `ms_per_step`, the
+`roofline` of the timed launches and the map's checksum.  Everything else below (`others`, `pointwise_kernels`,
+`cpu_baseline`, `bad1_vs_cpu_ref`, `e2e_host_arrays`, the fp32-vs-exact comparison and, with N > 1, the strips' map
+against one launch over the whole frame) takes runs of its own and is measured only with --full.
+--dump-outputs DIR writes the disparity map of the last timed step (rank 0's gathered map with N > 1) to
+DIR/disparity.npy as float32.
 
 Both forms work: started WITHOUT a launcher (no WORLD_SIZE in the environment) and with --gpus N > 1, bench.py
 re-executes itself under torch.distributed.run on a free local port -- one rank per GPU over RCCL -- and passes rank 0's
@@ -103,7 +110,8 @@ def count_taps(H, W, win, maxD, minD, row0=0, rows=None):
     return int(vrows.sum()) * int(cols.sum())
 
 
-def cpu_baseline(cfg, seed, rows_per_thread=1, timeout_s=300, crop_cols=512, repeats=2, pin_cores=32, pinned_rows_per_core=4):
+def cpu_baseline(cfg, seed, rows_per_thread=1, timeout_s=300, crop_cols=512, repeats=2, pin_cores=32, pinned_rows_per_core=4,
+                 budget_s=360):
     """Time the reference (and the hoisted plain-C port) on a bounded crop of the same frame, on the host cores.
 
     The reference hands out ONE image row per job to hardware_concurrency() threads (_passive.cpp:352-355, 372-396).
@@ -175,9 +183,12 @@ print(json.dumps({"t": dt, "kind": kind, "r0": int(r0), "cpu_s": (ru1.ru_utime -
     dump_a = os.path.join(tempfile.gettempdir(), "ssamd_cpu_all_%d.npy" % os.getpid())
     dump_h = os.path.join(tempfile.gettempdir(), "ssamd_cpu_hoist_%d.npy" % os.getpid())
 
+    deadline = time.time() + budget_s       # all samples together: a hung sample must not hold up the --full run past its limit
+
     def run(rows, mode, path, pin):
+        wait = max(1.0, min(timeout_s, deadline - time.time()))
         out = subprocess.run([sys.executable, "-c", code, str(rows), path, mode, str(c0), str(cols), str(pin)], capture_output=True,
-                             text=True, timeout=timeout_s)      # the reference's queue has an empty()/pop() race: bounded wait
+                             text=True, timeout=wait)      # the reference's queue has an empty()/pop() race: bounded wait
         res = json.loads(out.stdout.strip().splitlines()[-1])
         res["rows"] = rows
         return res
@@ -648,6 +659,22 @@ def relaunch_under_torchrun(n):
     return subprocess.call(cmd, env=env)
 
 
+DUMP_LIMIT = 64 << 20   # bytes: all arrays --dump-outputs writes, together
+
+
+def dump_outputs(dirpath, arrays):
+    """--dump-outputs: each tensor / array of `arrays` as <dirpath>/<name>.npy in float32 (int16 disparities are exact there)."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    host = {k: np.ascontiguousarray((v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)).astype(np.float32))
+            for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT))
+    for k, a in host.items():
+        np.save(os.path.join(dirpath, k + ".npy"), a)
+
+
 LINE_LIMIT = 8192       # bytes: the driver's parser gave up on the ~20 KB line of round 5 (BENCH_r05.json "parsed": null)
 
 
@@ -761,7 +788,17 @@ def main():
     ap.add_argument("--selftest-launcher", action="store_true",
                     help="CPU + gloo self-test of the rank launcher and the strip plumbing with a probe matcher (no GPU, "
                          "not a measurement): tests/test_bench_launcher_cpu.py")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beyond the headline figure: the other "
+                         "configurations, the pointwise kernels, the CPU baseline, the accuracy against the reference's maps, the "
+                         "host-array timings, the fp32-vs-exact comparison and (N > 1) the strips' map against one launch")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the disparity map of the last timed step to DIR/disparity.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(relaunch_under_torchrun(args.gpus))
@@ -910,8 +947,10 @@ def main():
             rccl["exchange_hidden"] = bool(max(ex) < 0.05)
             rccl["exchange_exposed_ms_max"] = max(ex)
     checksum = int(out.to(torch.int64).sum().item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"disparity": out})
     bad1_dist = None
-    if world > 1 and not args.no_bad1:
+    if world > 1 and args.full and not args.no_bad1:
         # the accuracy half of the metric THROUGH the distributed path (every rank takes part; rank 0 keeps the figures)
         try:
             bad1_dist = bad1_on_reference_strips(dev, rank, world, consistent=args.consistent, config=args.config)
@@ -975,12 +1014,13 @@ def main():
                 line["roofline"].update({"frac": slow["valu_frac"], "kernel_ms": slow["kernel_ms"], "taps_per_launch": slow["taps"],
                                          "achieved": VALU_OPS_PER_TAP * slow["taps"] / (slow["kernel_ms"] * 1e-3),
                                          "of_rank": slow["rank"], "note": "the slowest rank's strip"})
-            try:
-                single = matcher.compute(torch.from_numpy(L).to(dev), torch.from_numpy(R).to(dev))
-                line["config"]["checksum_single_gpu"] = int(single.to(torch.int64).sum().item())
-                line["config"]["checksum_equals_single_gpu"] = bool(torch.equal(single, out.to(single.device)))
-            except Exception as e:      # noqa: BLE001
-                line["config"]["checksum_equals_single_gpu"] = repr(e)[:160]
+            if args.full:
+                try:
+                    single = matcher.compute(torch.from_numpy(L).to(dev), torch.from_numpy(R).to(dev))
+                    line["config"]["checksum_single_gpu"] = int(single.to(torch.int64).sum().item())
+                    line["config"]["checksum_equals_single_gpu"] = bool(torch.equal(single, out.to(single.device)))
+                except Exception as e:      # noqa: BLE001
+                    line["config"]["checksum_equals_single_gpu"] = repr(e)[:160]
             if bad1_dist is not None:
                 line["bad1_vs_cpu_ref"] = bad1_dist
         line["default_mode"] = ("exact: StereoASW(exact=\"auto\") -- near-ties of every winner selected in the aggregation kernel and re-decided in "
@@ -988,7 +1028,7 @@ def main():
                                "fp32 argmin only (--fp32: StereoASW(exact=False)); NOT the default path"
         if launches[_native.K_ASW_EXACT]:
             line["exact_pass_ms"] = ms[_native.K_ASW_EXACT] / max(1, args.steps)
-        if world == 1 and not use_dist and not args.fp32:
+        if world == 1 and not use_dist and not args.fp32 and args.full:
             # the same frame WITHOUT the tie-break pass (the default of rounds 1-5), alternating with the default so that both see the
             # same clocks: what the reference's own map costs
             try:
@@ -1019,7 +1059,7 @@ def main():
             line["alternate_rows_mode"] = {"ms_per_step": (time.perf_counter() - ta) / 3 * 1e3,
                                            "percent_pixels_differing_from_exact": 100.0 * float((alt_map != out).float().mean()),
                                            "note": "opt-in StereoASW(alternate=True); not the reference's output, never `value`"}
-        if world == 1 and not args.no_others:
+        if world == 1 and args.full and not args.no_others:
             line["others"] = others(dev, args.seed)
             # the pointwise kernels either side of the matchers (Lab records, rectification remap, 3-D reprojection)
             # against the HBM roofline: tools/bench_pointwise.py
@@ -1029,12 +1069,12 @@ def main():
                 line["pointwise_kernels"] = bench_pointwise.measure()
             except Exception as e:      # noqa: BLE001
                 line["pointwise_kernels"] = {"error": repr(e)[:200]}
-        if world == 1 and not use_dist and not args.no_bad1:
+        if world == 1 and not use_dist and args.full and not args.no_bad1:
             try:
                 line["bad1_vs_cpu_ref"] = bad1_on_reference_strips(dev, consistent=args.consistent, config=args.config)
             except Exception as e:      # noqa: BLE001
                 line["bad1_vs_cpu_ref"] = {"percent": None, "source": repr(e)[:200]}
-        if world == 1 and not use_dist and not args.no_e2e:
+        if world == 1 and not use_dist and args.full and not args.no_e2e:
             try:
                 resident = {args.config: per_step * 1e3}
                 for k in ("default_1080p_d16_w35", "c1_tsukuba_d16_w15"):
@@ -1043,7 +1083,7 @@ def main():
                 line["e2e_host_arrays"] = e2e_host_arrays(args.seed, resident)
             except Exception as e:      # noqa: BLE001
                 line["e2e_host_arrays"] = {"error": repr(e)[:200]}
-        if world == 1 and not use_dist and not args.no_cpu_baseline:
+        if world == 1 and not use_dist and args.full and not args.no_cpu_baseline:
             cb = cpu_baseline(cfg, args.seed, args.cpu_rows_per_thread, crop_cols=args.cpu_crop_cols or cfg[1], repeats=args.cpu_repeats,
                               pin_cores=args.cpu_pin_cores, pinned_rows_per_core=args.cpu_pinned_rows_per_core)
             # second half of BASELINE's metric: % bad-1.0 of the GPU map vs the CPU reference map, on the strip

@@ -86,3 +86,23 @@ def test_compact_line_of_the_largest_committed_records_stays_under_8_kb(record):
     else:
         assert len(line["rccl"]["ranks"]) == full["n_gpus"] and line["rccl"]["world_size"] == full["n_gpus"]
     assert not any(isinstance(v, str) and len(v) > 260 for v in line.values())
+
+
+def test_dump_outputs_writes_float32_arrays_within_the_size_limit(tmp_path):
+    """--dump-outputs: one <name>.npy per array, float32, values unchanged; more than 64 MB in all is refused"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    d = np.random.default_rng(3).integers(-1, 257, (37, 50)).astype(np.int16)
+    bench.dump_outputs(str(tmp_path / "out"), {"disparity": d})
+    got = np.load(str(tmp_path / "out" / "disparity.npy"))
+    assert got.dtype == np.float32 and got.shape == d.shape and np.array_equal(got, d.astype(np.float32))
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"a": np.zeros(bench.DUMP_LIMIT // 4 + 1, np.int8)})
+    assert not (tmp_path / "big" / "a.npy").exists()
+
+
+def test_bench_refuses_zero_steps():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--selftest-launcher"], capture_output=True,
+                       text=True, timeout=300, env=_clean_env(), cwd=ROOT)
+    assert r.returncode != 0 and "--steps" in r.stderr

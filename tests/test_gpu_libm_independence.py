@@ -33,7 +33,7 @@ DRIVER = r"""
 import ctypes, json, os, sys
 import numpy as np
 sys.path.insert(0, sys.argv[1])
-shim = ctypes.CDLL(os.environ["LD_PRELOAD"])
+shim = ctypes.CDLL(sys.argv[2])
 libm = ctypes.CDLL("libm.so.6"); libm.exp.restype = ctypes.c_double; libm.exp.argtypes = [ctypes.c_double]
 import simplestereo_amd as ss
 G = os.path.join(sys.argv[1], "tests", "golden")
@@ -68,8 +68,10 @@ def test_asw_maps_with_the_process_libm_poisoned(tmp_path):
     subprocess.check_call(["gcc", "-O1", "-shared", "-fPIC", "-fno-builtin", "-o", str(so), str(src)])
     drv = tmp_path / "driver.py"
     drv.write_text(DRIVER)
-    env = dict(os.environ, LD_PRELOAD=str(so), SSAMD_AUTOTUNE="0")
-    r = subprocess.run([sys.executable, str(drv), ROOT], capture_output=True, text=True, timeout=900, env=env, cwd=str(tmp_path))
+    # the shim goes first; whatever the environment already preloads stays preloaded behind it
+    preload = " ".join([str(so)] + ([os.environ["LD_PRELOAD"]] if os.environ.get("LD_PRELOAD") else []))
+    env = dict(os.environ, LD_PRELOAD=preload, SSAMD_AUTOTUNE="0")
+    r = subprocess.run([sys.executable, str(drv), ROOT, str(so)], capture_output=True, text=True, timeout=900, env=env, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
     res = json.loads([l for l in r.stdout.splitlines() if l.startswith("RESULT ")][-1][7:])
     assert abs(res["exp_of_1"] - 0.126) < 1e-9, res                 # the shim IS what exp() resolves to in that process

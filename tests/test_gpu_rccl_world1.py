@@ -124,7 +124,7 @@ def test_bench_line_of_a_two_rank_run_explains_itself(tmp_path):
         env.pop(k, None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--config", "c2_480p_d64_w35"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                        "--config", "c2_480p_d64_w35", "--full"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     compact, line = _read(r, env)
     assert compact["n_gpus"] == 2 and compact["rccl"]["world_size"] == 2 and len(compact["rccl"]["ranks"]) == 2
@@ -156,7 +156,7 @@ def test_bench_line_carries_the_contract_keys(tmp_path):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "SSAMD_BENCH_FORCE_DIST"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--config", "c2_480p_d64_w35",
-                        "--no-others", "--no-e2e", "--cpu-crop-cols", "96"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                        "--full", "--no-others", "--no-e2e", "--cpu-crop-cols", "96"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     assert len([l for l in r.stdout.splitlines() if l.strip()]) == 1, r.stdout
     compact, line = _read(r, env)
@@ -196,3 +196,30 @@ def test_bench_line_carries_the_contract_keys(tmp_path):
     assert b["percent"] <= 0.5 and b["pixels"] == 1080 * 1920 and b["headline_case"] == "F3p" and b["exact_percent"] >= 99.0
     # ... and the same frame through StereoASW(exact=True): the reference's map itself
     assert b["exact_mode"]["differing_pixels"] == 0 and b["exact_mode"]["pixels"] == 1080 * 1920 and b["exact_mode"]["queue_overflow"] == 0
+
+
+def test_plain_bench_run_times_the_steps_and_dumps_the_last_map(tmp_path):
+    """a plain run (no --full) prints the headline line and nothing that takes runs of its own; --dump-outputs writes the map of
+    the last timed step, which for config 2's geometry on make_pair(480, 640, 64, seed=0) is the reference's map G6f"""
+    import numpy as np
+    env = _details(dict(os.environ), tmp_path)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "SSAMD_BENCH_FORCE_DIST"):
+        env.pop(k, None)
+    dump = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--config",
+                        "c2_480p_d64_w35", "--seed", "0", "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600,
+                       env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert len([l for l in r.stdout.splitlines() if l.strip()]) == 1, r.stdout
+    compact, line = _read(r, env)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "roofline"):
+        assert k in compact, k
+    assert compact["steps"] == 3 and compact["warmup"] == 1 and compact["ms_per_step"] > 0 and compact["higher_is_better"] is True
+    assert abs(compact["value"] - 480 * 640 * 65 / (compact["ms_per_step"] * 1e-3) / 1e6) < 1e-6 * compact["value"]
+    for k in ("cpu_baseline", "bad1_vs_cpu_ref", "others", "pointwise_kernels", "e2e_host_arrays", "fp32_ms_per_step"):
+        assert k not in line, k
+    d = np.load(str(dump / "disparity.npy"))
+    assert d.dtype == np.float32 and d.shape == (480, 640)
+    assert int(d.astype(np.int64).sum()) == line["config"]["checksum"]
+    want = np.load(os.path.join(ROOT, "tests", "golden", "cases.npz"))["G6f"]
+    assert np.array_equal(d, want.astype(np.float32))
