@@ -11,6 +11,8 @@
  *                           called from StereoASW.compute, passive.py:88-90
  *   ssamd_gsw          <->  _passive.computeGSW   simplestereo/_passive.cpp:703-774
  *                           called from StereoGSW.compute, passive.py:153-156
+ *   ssamd_iir_unwrap   <->  _unwrapping.infiniteImpulseResponse   simplestereo/_unwrapping.cpp:50-156
+ *                           called from unwrapping.infiniteImpulseResponse, unwrapping.py:10-41
  *   ssamd_*_device     same operators on buffers already resident in HBM (no
  *                      reference counterpart: the reference has no device).
  *
@@ -37,7 +39,7 @@
 extern "C" {
 #endif
 
-#define SSAMD_ABI_VERSION 5      /* 5: ssamd_asw_exact_device_rows2 / _rectified_device (round 6: near-ties selected inside the aggregation kernels); 4: ssamd_asw_exact* (round 5); 3: GSW autotuning; 2: ssamd_set_option (round 3) + the multi-device and verification entry points added in round 2 */
+#define SSAMD_ABI_VERSION 6      /* 6: ssamd_iir_unwrap / ssamd_iir_unwrap_device and profile slot SSAMD_K_UNWRAP; 5:ssamd_asw_exact_device_rows2 / _rectified_device (round 6: near-ties selected inside the aggregation kernels); 4: ssamd_asw_exact* (round 5); 3: GSW autotuning; 2: ssamd_set_option (round 3) + the multi-device and verification entry points added in round 2 */
 
 #define SSAMD_OK 0
 #define SSAMD_EINVAL (-1)     /* bad argument (message tells which)            */
@@ -234,6 +236,16 @@ int ssamd_gsw_rectified_device(const uint8_t *d_raw1, const uint8_t *d_raw2, int
  * d_points 16-byte aligned (any device allocation is). */
 int ssamd_reproject_device(const int16_t *d_disparity, int h, int w, const double *Q, float *d_points, void *stream);
 
+/* ---- phase unwrapping (the reference's second native extension) -------------- */
+/* _unwrapping.infiniteImpulseResponse(phase, tau) (reference _unwrapping.cpp:50-156): the infinite-impulse-response unwrapper
+ * of Estrada et al. 2011 on n C-contiguous fp64 maps [h][w] (a batch is n consecutive maps), output fp64 [n][h][w] equal to
+ * the reference's bit for bit -- same operands, same order, fp64, no contraction, a true division (csrc/unwrap_kernels.hip.h:
+ * a skewed wavefront, one workgroup per map).  Checks as the reference: h, w >= 1 ("Wrong phase dimensions!"), 0 <= tau <= 1
+ * ("Wrong tau value!"; NaN passes and gives NaN maps); n = 0 does nothing.  SSAMD_ELIMIT for w > 16384.
+ * ssamd_iir_unwrap: host buffers, synchronous.  ssamd_iir_unwrap_device: device buffers, asynchronous on `stream`. */
+int ssamd_iir_unwrap(const double *phase, int n, int h, int w, double tau, double *out, int device);
+int ssamd_iir_unwrap_device(const double *d_phase, int n, int h, int w, double tau, double *d_out, void *stream);
+
 /* ---- verification / measurement helpers ------------------------------------ */
 
 /* Raw left-referenced aggregated ASW costs, float32 [height][width][nD] with
@@ -289,7 +301,8 @@ int ssamd_debug_gsw_sqrt(int n, float *out);
 #define SSAMD_K_REPROJECT 6  /* disparity -> 3-D points                           */
 #define SSAMD_K_ASW_ALT 7    /* alternate-rows mode: bounded search on the odd rows */
 #define SSAMD_K_ASW_EXACT 8  /* fp64 tie-break pass of ssamd_asw_exact* (fp64 Lab, filter, winners, eval, resolve, patch) */
-#define SSAMD_K_COUNT 9
+#define SSAMD_K_UNWRAP 9     /* phase unwrapping wavefront (iir_unwrap_kernel)                                     */
+#define SSAMD_K_COUNT 10
 int ssamd_profile_enable(int on);
 int ssamd_profile_reset(void);
 int ssamd_profile_read(double *ms /*[SSAMD_K_COUNT]*/, long long *launches /*[SSAMD_K_COUNT]*/);

@@ -15,6 +15,7 @@ from . import passive
 from ._rigs import StereoRig, RectifiedStereoRig
 from . import strips
 from . import points
+from . import unwrapping
 
 __version__ = "0.6.0"
-__all__ = ["passive", "StereoRig", "RectifiedStereoRig", "strips", "points"]
+__all__ = ["passive", "StereoRig", "RectifiedStereoRig", "strips", "points", "unwrapping"]

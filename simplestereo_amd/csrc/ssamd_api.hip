@@ -39,6 +39,7 @@ namespace ssamd {
 #include "lab_kernels.hip.h"
 #include "asw_exact_kernels.hip.h"
 #include "rig_kernels.hip.h"
+#include "unwrap_kernels.hip.h"
 
 using namespace ssamd;
 
@@ -88,6 +89,7 @@ struct Tuning {
     int exact_tol = 128;              // fp64 tie-break pass: candidates within this many ulps of the winning cost image are re-evaluated
     int exact_cap = 0;                // 0 unset: queue capacity of the tie-break pass in entries (test hook: a tiny queue overflows)
     int exact_rawcap = 0;             // 0 unset: capacity of the RAW queue of merging calls (test hook)
+    int unwrap_rows = 0;              // 0 unset: most rows per band of the unwrapping wavefront (64..1024, rounded up to 64)
 };
 std::mutex g_tune_mutex;
 std::atomic<unsigned> g_tune_version{1};
@@ -121,6 +123,7 @@ bool tuning_assign(Tuning &t, const std::string &name, const char *v)
     else if (name == "SSAMD_EXACT_TOL") t.exact_tol = v ? std::max(0, atoi(v)) : 128;
     else if (name == "SSAMD_EXACT_CAP") t.exact_cap = v ? std::max(1, atoi(v)) : 0;
     else if (name == "SSAMD_EXACT_RAWCAP") t.exact_rawcap = v ? std::max(1, atoi(v)) : 0;
+    else if (name == "SSAMD_UNWRAP_ROWS") t.unwrap_rows = v ? std::max(0, std::min(UNWRAP_MAX_ROWS, atoi(v))) : 0;
     else return false;
     return true;
 }
@@ -129,7 +132,7 @@ const char *const kTuningNames[] = {"SSAMD_ASW_GEOM", "SSAMD_GSW_GEOM", "SSAMD_A
                                     "SSAMD_ASW_WAVE", "SSAMD_ASW_WAVE_RX", "SSAMD_ASW_WAVE_WG", "SSAMD_ASW_WAVE_UNROLL",
                                     "SSAMD_ASW_WAVE_MERGE", "SSAMD_ASW_STATIC", "SSAMD_ASW_EVOL_MAX_MB", "SSAMD_ASW_WAVE_RD", "SSAMD_ASW_NO_E2", "SSAMD_ASW_XOR_ONLY", "SSAMD_MULTI_ALLOW_REPEAT",
                                     "SSAMD_ALT_QUEUE_CAP", "SSAMD_AUTOTUNE", "SSAMD_ASW_EVOL_FAIL", "SSAMD_ASW_TAIL", "SSAMD_ASW_WAVE_CREG", "SSAMD_ASW_LDS_RELAX",
-                                    "SSAMD_EXACT_TOL", "SSAMD_EXACT_CAP", "SSAMD_EXACT_RAWCAP", "SSAMD_ASW_PREPASS_FUSE"};
+                                    "SSAMD_EXACT_TOL", "SSAMD_EXACT_CAP", "SSAMD_EXACT_RAWCAP", "SSAMD_ASW_PREPASS_FUSE", "SSAMD_UNWRAP_ROWS"};
 
 std::map<std::string, std::string> g_tuning_env;      // what the process was started with: ssamd_set_option(name, NULL) goes back to THIS
 Tuning tuning_from_env()
@@ -252,6 +255,7 @@ struct Ctx {
     hipStream_t stream = nullptr;       // used by the host-buffer entry points
     DevBuf imgL, imgR, recL, recR, keyL, keyR, disp, costs, lab, altq, evol, altdisp;
     DevBuf xlabL, xlabR, xflags, xqueue, xcost, xslots, xctr, xraw, xwtab;      // fp64 tie-break pass (asw_exact_kernels.hip.h)
+    DevBuf uwIn, uwOut;                 // host-buffer phase unwrapping (unwrap_kernels.hip.h)
     unsigned int xcap = 0, xrawcap = 0; // queue capacities of the last exact call
     TableCache proxTabs{8}, gswTabs{4}, proxTabs64{8};
     std::map<const void *, int> max_dyn_lds;   // hipFuncAttributeMaxDynamicSharedMemorySize already granted per kernel
@@ -2019,7 +2023,8 @@ const char *ssamd_kernel_name(int slot)
     static const char *names[SSAMD_K_COUNT] = {"asw pre-pass (asw_prepass_kernel: Lab records + TAD volume; or bgr2lab_records_pair_kernel, asw_tad_volume_kernel)", "asw aggregation kernel (asw_aggregate_pipe / _wave / asw_aggregate_kernel)",
                                                "asw finalize (wta_decode / lr_check_fill)",
                                                "gsw_aggregate_kernel", "gsw finalize (lr_check_fill)", "remap_bgr_kernel", "reproject_kernel",
-                                               "asw_alt_fill_kernel", "asw fp64 tie-break pass (bgr2lab_f64_pair + asw_exact_winners / _eval / _resolve / _patch kernels)"};
+                                               "asw_alt_fill_kernel", "asw fp64 tie-break pass (bgr2lab_f64_pair + asw_exact_winners / _eval / _resolve / _patch kernels)",
+                                               "iir_unwrap_kernel"};
     return (slot >= 0 && slot < SSAMD_K_COUNT) ? names[slot] : "";
 }
 
@@ -2501,6 +2506,69 @@ int ssamd_reproject_device(const int16_t *d_disparity, int h, int w, const doubl
     hipLaunchKernelGGL(reproject_kernel, dim3((per_row + 255) / 256, h), dim3(256), 0, s, d_disparity, d_points, h, w, q);
     HIP_TRY(hipGetLastError());
     return SSAMD_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// _unwrapping.infiniteImpulseResponse's checks (_unwrapping.cpp:63-74) on n [h][w] maps, plus the kernel's own limits
+int unwrap_check(int n, int h, int w, double tau)
+{
+    if (n < 0 || h <= 0 || w <= 0) return fail(SSAMD_EINVAL, "Wrong phase dimensions!");
+    if (tau < 0 || tau > 1) return fail(SSAMD_EINVAL, "Wrong tau value!");                   // NaN passes, as in the reference
+    if (w > UNWRAP_MAX_W) return fail(SSAMD_ELIMIT, "phase maps wider than %d columns are not supported (width %d)", UNWRAP_MAX_W, w);
+    if ((long long)h * w > (1ll << 40)) return fail(SSAMD_ELIMIT, "phase map of %d x %d pixels too large", h, w);
+    return SSAMD_OK;
+}
+
+// One workgroup per map.  Bands as few as the row cap allows, their heights as even as whole waves make them: the step count,
+// bands * w + 2 (h - bands), depends on the number of bands only, and fewer waves per workgroup share the CU's SIMDs.
+int unwrap_launch(Ctx &c, const double *d_phase, int n, int h, int w, double tau, double *d_out, hipStream_t s)
+{
+    if (n == 0) return SSAMD_OK;
+    const int cap = tune().unwrap_rows > 0 ? round_up(tune().unwrap_rows, 64) : UNWRAP_MAX_ROWS;
+    const int bands = (h + cap - 1) / cap;
+    const int R = round_up((h + bands - 1) / bands, 64);
+    const int lds = (w + 2 * R) * (int)sizeof(double);
+    int rc = grant_dyn_lds(c, reinterpret_cast<const void *>(&iir_unwrap_kernel), lds);
+    if (rc) return rc;
+    Timed t(c, s, SSAMD_K_UNWRAP);
+    hipLaunchKernelGGL(iir_unwrap_kernel, dim3(n), dim3(R), lds, s, d_phase, d_out, h, w, tau);
+    HIP_TRY(hipGetLastError());
+    return SSAMD_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int ssamd_iir_unwrap(const double *phase, int n, int h, int w, double tau, double *out, int device)
+{
+    if (!phase || !out) return fail(SSAMD_EINVAL, "NULL buffer");
+    int rc = unwrap_check(n, h, w, tau);
+    if (rc) return rc;
+    if (n == 0) return SSAMD_OK;
+    CtxLock c;
+    if ((rc = get_ctx(device, c))) return rc;
+    const size_t bytes = (size_t)n * h * w * sizeof(double);
+    if ((rc = c->uwIn.reserve(bytes)) || (rc = c->uwOut.reserve(bytes))) return rc;
+    hipStream_t s = c->stream;
+    ScratchOrder order(*c, s);
+    HIP_TRY(hipMemcpyAsync(c->uwIn.ptr, phase, bytes, hipMemcpyHostToDevice, s));
+    if ((rc = unwrap_launch(*c, (const double *)c->uwIn.ptr, n, h, w, tau, (double *)c->uwOut.ptr, s))) return rc;
+    HIP_TRY(hipMemcpyAsync(out, c->uwOut.ptr, bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return SSAMD_OK;
+}
+
+int ssamd_iir_unwrap_device(const double *d_phase, int n, int h, int w, double tau, double *d_out, void *stream)
+{
+    if (!d_phase || !d_out) return fail(SSAMD_EINVAL, "NULL buffer");
+    int rc = unwrap_check(n, h, w, tau);
+    if (rc) return rc;
+    if (n == 0) return SSAMD_OK;
+    CtxLock c;
+    if ((rc = get_ctx(-1, c))) return rc;
+    return unwrap_launch(*c, d_phase, n, h, w, tau, d_out, (hipStream_t)stream);
 }
 
 namespace {
