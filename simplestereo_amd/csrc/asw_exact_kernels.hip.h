@@ -114,11 +114,11 @@ __global__ __launch_bounds__(256) void asw_exact_filter_kernel(const AswExactArg
             const uint32_t esc = 0xC0000000u - __float_as_uint(2.0f * A.q.sat_abs);      // (escalated pixels get every candidate from asw_exact_escalate_kernel)
             if (sides & EXACT_SIDE_L) {
                 const u64 g = A.keyL[pix];
-                if ((int)(uint32_t)g != d && (uint32_t)(g >> 32) < esc && exact_near(key, (uint32_t)(g >> 32), A.q.tol, A.q.sat_abs)) s2 |= EXACT_SIDE_L;
+                if ((int)(uint32_t)g != d && (uint32_t)(g >> 32) < esc && exact_near(key, (uint32_t)(g >> 32), A.q.tol, A.q.sat_abs, exact_zkey(A.win))) s2 |= EXACT_SIDE_L;
             }
             if ((sides & EXACT_SIDE_R) && A.keyR) {
                 const u64 g = A.keyR[pix - (uint32_t)d];
-                if ((uint32_t)g != pix % (uint32_t)A.W && (uint32_t)(g >> 32) < esc && exact_near(key, (uint32_t)(g >> 32), A.q.tol, A.q.sat_abs)) s2 |= EXACT_SIDE_R;
+                if ((uint32_t)g != pix % (uint32_t)A.W && (uint32_t)(g >> 32) < esc && exact_near(key, (uint32_t)(g >> 32), A.q.tol, A.q.sat_abs, exact_zkey(A.win))) s2 |= EXACT_SIDE_R;
             }
         }
         asw_exact_push_wave(A.q, s2 != 0, pix, d, s2, rkey);
@@ -168,8 +168,9 @@ __global__ __launch_bounds__(256) void asw_exact_escalate_kernel(const AswExactA
     }
 }
 
-// 1d. Pixels with TWO OR MORE candidates whose fp32 cost is EXACTLY 0 (N = 0; marked by asw_exact_select / asw_exact_merge -- a lone zero,
-// the true match of a synthetic pair, needs nothing).  Candidates with image 0 are not queued: deep inside the black margins of a
+// 1d. Pixels with TWO OR MORE candidates whose fp32 cost is EXACTLY 0 (N = 0; marked by asw_exact_select / asw_exact_merge -- a lone zero
+// is no tie of another zero, but its fp64 cost may exceed a rival's tiny positive one: rule (d) of exact_near, exact_zkey,
+// queues every candidate up to win^2 * 40 * 2^-126 * 2).  Candidates with image 0 are not queued: deep inside the black margins of a
 // rectified frame every candidate of a pixel is one -- 3e7 entries at 1080p.  The reference's cost of such a candidate is
 // exactly 0.0 iff every in-image tap has TAD = 0 (weights are positive in fp64), and costs are >= 0: if the fp32 winner -- the smallest
 // index among the candidates with image 0 -- passes that integer test, it IS the reference's first minimum (smaller indices have N > 0

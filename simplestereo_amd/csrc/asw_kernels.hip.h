@@ -71,7 +71,7 @@ struct AswExactQueue {
     unsigned int *counter;       // entries appended (may exceed cap)
     unsigned char *flagL, *flagR;    // [rows][W] the pixel has near-ties (flagR null: no right-referenced pass; both null: RAW queue)
     unsigned char *zeroL, *zeroR;    // [rows][W] the (left / right) pixel has TWO OR MORE candidates whose fp32 cost is exactly 0: asw_exact_zero_kernel
-                                     //   (a lone zero -- the true match of a synthetic pair -- needs nothing; zeroR null without a right pass)
+                                     //   (a lone zero is covered by rule (d) of exact_near; zeroR null without a right pass)
     unsigned char *zrow;             // [rows] the row holds such a pixel: only those rows are looked at
     unsigned int W;                  // image width (row of a pixel index)
     unsigned int cap;
@@ -247,6 +247,16 @@ __device__ __forceinline__ uint32_t asw_cost_key(const float n, const float s, f
 
 // ---- exact mode: near-tie selection (shared by the four kernel families) ------------------------------------------------
 static constexpr unsigned EXACT_SIDE_L = 1u, EXACT_SIDE_R = 2u;
+// Rule (d)'s floor: the cost image of Z = 2 * win^2 * 40 * 2^-126 (below 20: the image is the float's bits).  A winner whose fp32
+// cost is 0 while taps with TAD > 0 are in its window owes that 0 to flushed weights (v_exp_f32 returns no denormals): each such
+// weight is below 2^-126 in fp64, and the weights sum to >= 1 (the centre tap), so the reference's cost is at most Z / 2.  `tol`
+// ulps of 0 are a few denormals: a rival with a tiny positive cost that the reference ranks first would not be queued.  Computed
+// from the window (a compile-time constant in the phase-shifted kernel's static instances) rather than carried in AswExactQueue:
+// one kernel-argument SGPR more in the headline kernel cost 0.4 % of the bench step.  (5 * 2^-122 = 80 * 2^-126 exactly.)
+__device__ __forceinline__ uint32_t exact_zkey(int win)
+{
+    return __float_as_uint((float)(win * win) * 9.4039548065783e-37f);
+}
 // hint bit of a queue entry: the candidate's fp32 cost image is 0 (N = 0 exactly).  Black margins of rectified frames tie thousands
 // of such candidates per row; the fp64 cost of one is EXACTLY 0 iff every in-image tap has TAD = 0 (weights are positive in
 // fp64), which asw_exact_eval_kernel checks with integer compares before it spends ~2 500 fp64 exp / sqrt / div on the entry
@@ -258,13 +268,14 @@ static constexpr uint32_t EXACT_KEY_HIGH = 0xC0000000u - 0x41A00000u;      // 0x
 // saturated side of the image (cost > 20: the image holds 40 - cost), within `sat_abs` in ABSOLUTE terms: the (N, S') pair
 // resolves 40 - 1e-30 from 40 - 0, but the reference's fp64 quotient carries a rounding noise of up to ~(win^2) ulps of 40
 // (2e-11 for a 35 x 35 window), so among candidates closer than that its first minimum is decided by that noise and has to be
-// recomputed -- or (c) the two lie either side of cost = 20, where the image changes form and ulps do not compare.
+// recomputed -- or (c) the two lie either side of cost = 20, where the image changes form and ulps do not compare -- or (d) the
+// candidate's image is at most `zkey` (exact_zkey: twice the fp64 cost a winner whose fp32 cost flushed to 0 may have).
 // MONOTONE in kb: near(key, kb) implies near(key, kb') for every kb <= kb' <= key, except where (c) held for kb and kb' is on
 // the other side of 20 -- exact_near_local below closes that gap, so a workgroup may test against its tile-local winner
 // (>= the final one) and queue a superset.
-__device__ __forceinline__ bool exact_near(uint32_t key, uint32_t kb, uint32_t tol, float sat_abs)
+__device__ __forceinline__ bool exact_near(uint32_t key, uint32_t kb, uint32_t tol, float sat_abs, uint32_t zkey)
 {
-    if (key - kb <= tol) return true;
+    if (key - kb <= tol || key <= zkey) return true;
     if (key >= EXACT_KEY_HIGH) {
         const float inv = __uint_as_float(0xC0000000u - key);                                   // 40 - cost of the candidate
         if (kb >= EXACT_KEY_HIGH) return __uint_as_float(0xC0000000u - kb) - inv <= sat_abs;
@@ -275,13 +286,13 @@ __device__ __forceinline__ bool exact_near(uint32_t key, uint32_t kb, uint32_t t
 
 // ... against a winner kb' that may still be displaced by a better one: also true when both images are saturated-side and the
 // candidate is inside the band above cost 20 that case (c) spans (a final winner just below 20 would make it a near-tie)
-__device__ __forceinline__ bool exact_near_local(uint32_t key, uint32_t kb, uint32_t tol, float sat_abs)
+__device__ __forceinline__ bool exact_near_local(uint32_t key, uint32_t kb, uint32_t tol, float sat_abs, uint32_t zkey)
 {
-    if (key - kb <= tol) return true;
+    if (key - kb <= tol || key <= zkey) return true;
     // quick reject (the common case of the epilogue scan: a wrong candidate, cost > 20, of a pixel whose winner is well below 20):
     // cases (b), (c) and the band all need the winner within 20 * 2^-23 * tol <= 2.4 (tol <= 1e6) of cost = 20 or above it
     if (key < EXACT_KEY_HIGH || kb < 0x418C0000u) return false;          // 0x418C0000 = bits of 17.5f
-    if (exact_near(key, kb, tol, sat_abs)) return true;
+    if (exact_near(key, kb, tol, sat_abs, zkey)) return true;
     return kb >= EXACT_KEY_HIGH && __uint_as_float(0xC0000000u - key) >= 20.0f - 20.0f * 1.1920929e-7f * (float)tol;
 }
 
@@ -326,7 +337,7 @@ template <int RX, int RD> struct AswKeyTile { uint32_t v[RX][RD]; };
 //  phase-shifted kernel's VGPRs into scratch: the by-value tile travels THROUGH scratch, + 0.9 ms per 1080p launch.  Inlined it is.)
 template <int RX, int RD>
 __device__ __forceinline__ void asw_exact_select(const AswExactQueue &q, bool live, const AswKeyTile<RX, RD> &kt,
-                                                 const u64 *bL, const u64 *bR, int xb, int db, uint32_t rowpix)
+                                                 const u64 *bL, const u64 *bR, int xb, int db, uint32_t rowpix, uint32_t zkey)
 {
     const uint32_t (&kk)[RX][RD] = kt.v;
     static_assert(RX * RD <= 32, "one bit per candidate of the register tile");
@@ -336,7 +347,8 @@ __device__ __forceinline__ void asw_exact_select(const AswExactQueue &q, bool li
     // winner costs 17.5 or more -- one branch per column, skipped by waves that hold no such column.  Invalid candidates carry
     // 0xffffffff and are masked out, and so are, in a merging call, candidates at or above q.deep (see AswExactQueue) -- and candidates
     // whose image is 0 (cost exactly 0: they can only tie a winner that costs 0 too; the black margins of a rectified 1080p frame are
-    // 3e7 of them; asw_exact_zero_kernel settles those pixels with integer compares).
+    // 3e7 of them; asw_exact_zero_kernel settles those pixels with integer compares).  Rule (d) rides on rule (a): a column whose
+    // winner is at or below zkey tests key - kh <= max(tol, zkey - kh), i.e. key <= kh + tol or key <= zkey (key >= kh).
     uint32_t mL = 0, mR = 0;
     if (live) {
         uint32_t zl = 0, zr = 0;
@@ -355,13 +367,14 @@ __device__ __forceinline__ void asw_exact_select(const AswExactQueue &q, bool li
             const u64 kl = bL[xi];
             const uint32_t kh = (uint32_t)(kl >> 32);
             const uint32_t wd = (uint32_t)kl - (uint32_t)db;                    // winner's disparity relative to the tile (== di for the winner)
+            const uint32_t tk = kh <= zkey ? max(tol, zkey - kh) : tol;         // rules (a) and (d)
             uint32_t okm = 0;
 #pragma unroll
             for (int di = 0; di < RD; ++di) {
                 const uint32_t key = kk[xi][di];
                 const uint32_t ok = (key < deep ? 1u : 0u) & (key != 0u ? 1u : 0u) & (wd != (uint32_t)di ? 1u : 0u);
                 okm |= ok << di;
-                mL |= (ok & (key - kh <= tol ? 1u : 0u)) << (xi * RD + di);
+                mL |= (ok & (key - kh <= tk ? 1u : 0u)) << (xi * RD + di);
                 zl |= ((key == 0u ? 1u : 0u) & (wd != (uint32_t)di ? 1u : 0u)) << xi;       // a second candidate that costs exactly 0
             }
             if (kh >= 0x418C0000u && kh != 0xffffffffu) {                       // 17.5f
@@ -376,13 +389,14 @@ __device__ __forceinline__ void asw_exact_select(const AswExactQueue &q, bool li
                 const uint32_t kh = (uint32_t)(kr >> 32);
                 const uint32_t wx = (uint32_t)kr - (uint32_t)xb;                // winner's column relative to the tile (== xi for the winner)
                 const bool high = kh >= 0x418C0000u && kh != 0xffffffffu;
+                const uint32_t tk = kh <= zkey ? max(tol, zkey - kh) : tol;     // rules (a) and (d)
 #pragma unroll
                 for (int xi = 0; xi < RX; ++xi) {
                     const int di = xi + RD - 1 - k;
                     if (di >= 0 && di < RD) {                                   // (compile time)
                         const uint32_t key = kk[xi][di];
                         const uint32_t ok = (key < deep ? 1u : 0u) & (key != 0u ? 1u : 0u) & (wx != (uint32_t)xi ? 1u : 0u);
-                        uint32_t near = key - kh <= tol ? 1u : 0u;
+                        uint32_t near = key - kh <= tk ? 1u : 0u;
                         if (high) near |= slow(key, kh);
                         mR |= (ok & near) << (xi * RD + di);
                         zr |= ((key == 0u ? 1u : 0u) & (wx != (uint32_t)xi ? 1u : 0u)) << k;
@@ -447,14 +461,14 @@ __device__ __forceinline__ void asw_exact_select(const AswExactQueue &q, bool li
 // that is a near-tie of the FINAL winner is queued, by its own workgroup or by the one that displaced it; the final winner
 // itself never is (asw_exact_winners_kernel adds it for flagged pixels).  RIGHT: keys of a right pixel xcol, low word = left column.
 template <bool RIGHT>
-__device__ __forceinline__ void asw_exact_merge(const AswExactQueue &q, bool have, u64 mine, u64 old, uint32_t rowpix, int xcol)
+__device__ __forceinline__ void asw_exact_merge(const AswExactQueue &q, bool have, u64 mine, u64 old, uint32_t rowpix, int xcol, uint32_t zkey)
 {
     bool want = false;
     uint32_t pix = 0, key = 0;
     int d = 0;
     if (have && old != KEY_NONE) {
         const u64 lo = mine < old ? mine : old, hi = mine < old ? old : mine;
-        if ((uint32_t)(hi >> 32) < q.deep && (uint32_t)(hi >> 32) != 0u && exact_near_local((uint32_t)(hi >> 32), (uint32_t)(lo >> 32), q.tol, q.sat_abs)) {
+        if ((uint32_t)(hi >> 32) < q.deep && (uint32_t)(hi >> 32) != 0u && exact_near_local((uint32_t)(hi >> 32), (uint32_t)(lo >> 32), q.tol, q.sat_abs, zkey)) {
             want = true;
             key = (uint32_t)(hi >> 32);
             if (RIGHT) { const int xl = (int)(uint32_t)hi; pix = rowpix + (uint32_t)xl; d = xl - xcol; }
@@ -840,7 +854,7 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, RX == 8 ? 3 : 4) void asw_aggregat
         const bool live = tidf < g.XG * g.DG;
         const int xg = live ? tidf % g.XG : 0, dg = live ? tidf / g.XG : 0;
         asw_exact_select<RX, ASW_RD>(A.xq, live, kt, bestL + RX * xg, A.keyR ? bestR + (RX * xg - ASW_RD * dg + Dc - ASW_RD) : nullptr,
-                                     x0 + RX * xg, dlo + ASW_RD * dg, (uint32_t)orow);
+                                     x0 + RX * xg, dlo + ASW_RD * dg, (uint32_t)orow, exact_zkey(win));
     }
     if (A.disp) {
         for (int k = tid; k < Tx; k += nthr) {
@@ -856,7 +870,7 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, RX == 8 ? 3 : 4) void asw_aggregat
             const bool have = k < Tx && x < W && bestL[k < Tx ? k : 0] != KEY_NONE;
             const u64 mine = have ? bestL[k] : KEY_NONE;
             const u64 old = have ? atomicMin(&A.keyL[orow + x], mine) : KEY_NONE;
-            asw_exact_merge<false>(A.xq, have, mine, old, (uint32_t)orow, x);
+            asw_exact_merge<false>(A.xq, have, mine, old, (uint32_t)orow, x, exact_zkey(win));
         }
         if (A.keyR)
             for (int k0 = 0; k0 < nRc; k0 += nthr) {
@@ -864,7 +878,7 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, RX == 8 ? 3 : 4) void asw_aggregat
                 const bool have = k < nRc && (unsigned)xr < (unsigned)W && bestR[k < nRc ? k : 0] != KEY_NONE;
                 const u64 mine = have ? bestR[k] : KEY_NONE;
                 const u64 old = have ? atomicMin(&A.keyR[orow + xr], mine) : KEY_NONE;
-                asw_exact_merge<true>(A.xq, have, mine, old, (uint32_t)orow, xr);
+                asw_exact_merge<true>(A.xq, have, mine, old, (uint32_t)orow, xr, exact_zkey(win));
             }
         return;
     }

@@ -617,7 +617,7 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(
     if (xq) {
         const int xg = pk_xd & 0xffff, dg = pk_xd >> 16;
         asw_exact_select<RX, ASW_RD>(A.xq, tidf < nact, kt, bestL + RX * xg, A.keyR ? bestR + (RX * xg - ASW_RD * dg + Dc - ASW_RD) : nullptr,
-                                     x0 + RX * xg, dlo + ASW_RD * dg, (uint32_t)orow);
+                                     x0 + RX * xg, dlo + ASW_RD * dg, (uint32_t)orow, exact_zkey(win));
     }
     if (A.disp) {
         for (int k = tid; k < Tx; k += nthr) {
@@ -633,7 +633,7 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(
             const bool have = k < Tx && x < W && bestL[k < Tx ? k : 0] != KEY_NONE;
             const u64 mine = have ? bestL[k] : KEY_NONE;
             const u64 old = have ? atomicMin(&A.keyL[orow + x], mine) : KEY_NONE;
-            asw_exact_merge<false>(A.xq, have, mine, old, (uint32_t)orow, x);
+            asw_exact_merge<false>(A.xq, have, mine, old, (uint32_t)orow, x, exact_zkey(win));
         }
         if (A.keyR)
             for (int k0 = 0; k0 < nRc; k0 += nthr) {
@@ -641,7 +641,7 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(
                 const bool have = k < nRc && (unsigned)xr < (unsigned)W && bestR[k < nRc ? k : 0] != KEY_NONE;
                 const u64 mine = have ? bestR[k] : KEY_NONE;
                 const u64 old = have ? atomicMin(&A.keyR[orow + xr], mine) : KEY_NONE;
-                asw_exact_merge<true>(A.xq, have, mine, old, (uint32_t)orow, xr);
+                asw_exact_merge<true>(A.xq, have, mine, old, (uint32_t)orow, xr, exact_zkey(win));
             }
         return;
     }

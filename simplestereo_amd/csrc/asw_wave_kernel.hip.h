@@ -468,7 +468,7 @@ __global__ __launch_bounds__(256, RX == 8 ? SSAMD_WAVE8_OCC : SSAMD_WAVE4_OCC) v
     const bool xq = !WITH_COSTS && A.xq.entries != nullptr;          // exact mode: near-ties of the winners go to the fp64 pass's queue
     if (xq)
         asw_exact_select<RX, ASW_RD>(A.xq, active, kt, bestL + RX * xg, A.keyR ? bestR + (RX * xg - ASW_RD * dg + Dc - ASW_RD) : nullptr,
-                                 x0 + RX * xg, dlo + ASW_RD * dg, (uint32_t)orow);
+                                 x0 + RX * xg, dlo + ASW_RD * dg, (uint32_t)orow, exact_zkey(win));
     if (A.disp) {
         for (int k = lane; k < Txw; k += 64) {
             const int x = x0 + k;
@@ -483,7 +483,7 @@ __global__ __launch_bounds__(256, RX == 8 ? SSAMD_WAVE8_OCC : SSAMD_WAVE4_OCC) v
             const bool have = k < Txw && x < W && bestL[k < Txw ? k : 0] != KEY_NONE;
             const u64 mine = have ? bestL[k] : KEY_NONE;
             const u64 old = have ? atomicMin(&A.keyL[orow + x], mine) : KEY_NONE;
-            asw_exact_merge<false>(A.xq, have, mine, old, (uint32_t)orow, x);
+            asw_exact_merge<false>(A.xq, have, mine, old, (uint32_t)orow, x, exact_zkey(win));
         }
         if (A.keyR)
             for (int k0 = 0; k0 < nRcw; k0 += 64) {
@@ -491,7 +491,7 @@ __global__ __launch_bounds__(256, RX == 8 ? SSAMD_WAVE8_OCC : SSAMD_WAVE4_OCC) v
                 const bool have = k < nRcw && (unsigned)xr < (unsigned)W && bestR[k < nRcw ? k : 0] != KEY_NONE;
                 const u64 mine = have ? bestR[k] : KEY_NONE;
                 const u64 old = have ? atomicMin(&A.keyR[orow + xr], mine) : KEY_NONE;
-                asw_exact_merge<true>(A.xq, have, mine, old, (uint32_t)orow, xr);
+                asw_exact_merge<true>(A.xq, have, mine, old, (uint32_t)orow, xr, exact_zkey(win));
             }
         return;
     }
