@@ -113,7 +113,13 @@ def _remap(img, mapx, mapy, interpolation=INTER_LINEAR):
     uint8 images take that fixed-point path, with the common factor 32 divided out: ``(S + 512) >> 10``.  Every other
     dtype goes the way of OpenCV's non-uchar instantiations: float32 weights ``(1-fy)(1-fx)`` ... from the 1/32-pixel
     fractions, a float32 sum in tap order, and for uint16 / int16 ... ``saturate_cast`` = round half to EVEN
-    (``np.rint``) + clip; float images keep the float sum.  cv2 is absent in this environment: parity with cv2.remap
+    (``np.rint``) + clip; float images keep the float sum.
+    Coordinates outside every range -- NaN, +-inf, and anything whose product with 32 leaves the int32 range (2^26 and beyond)
+    -- sample nothing and give the border value 0: OpenCV's path is ``saturate_cast<short>(cvRound(v * 32) >> 5)`` and
+    ``cvRound`` of NaN or of an out-of-range double is INT_MIN on x86, a cell far outside the image.  Here the conversion
+    to int64 sends NaN / +-inf / beyond-int64 values to INT64_MIN and keeps the others as huge cells, outside the image
+    either way; the HIP kernels test for them explicitly (``remap_pixel``); ``oracle/rig_oracle.py`` states the rule.
+    cv2 is absent in this environment: parity with cv2.remap
     itself stays unpinned here (reference call: _rigs.py:564-565) -- tests/test_cv2_pins.py pins it wherever cv2 exists."""
     img = np.asarray(img)
     squeeze = img.ndim == 2
@@ -487,6 +493,8 @@ class RectifiedStereoRig(StereoRig):
             raise ValueError("device reprojection expects an int16 [H,W] tensor")
         d = disp.contiguous()
         h, w = int(d.shape[0]), int(d.shape[1])
+        if w % 4 == 0 and d.data_ptr() % 8:
+            d = d.clone()         # a view at an odd storage offset: the kernel reads four disparities per 8-byte load
         Q = np.ascontiguousarray(self.getQ(), dtype=np.float64)
         out = torch.empty((h, w, 3), dtype=torch.float32, device=d.device)
         with torch.cuda.device(d.device):

@@ -24,6 +24,10 @@ __device__ __forceinline__ uint32_t remap_pixel(const uint8_t *__restrict__ src,
                                                 int nearest)
 {
     typedef uint64_t __attribute__((aligned(1))) u64_unaligned;
+    // NaN, +-inf and coordinates of 2^26 and beyond (where v * 32 leaves the int32 range): OpenCV's cvRound gives INT_MIN for
+    // all of them, a cell far outside the image, so the pixel is the border value.  Tested before the conversions because
+    // the device converts NaN to the integer 0, which would sample around source pixel (0, 0).
+    if (!(fabsf(mx) < 0x1p26f && fabsf(my) < 0x1p26f)) return 0u;
     if (nearest) {
         const int xi = (int)rintf(mx), yi = (int)rintf(my);
         if ((unsigned)xi < (unsigned)Ws && (unsigned)yi < (unsigned)Hs) {

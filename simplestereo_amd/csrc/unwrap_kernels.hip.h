@@ -27,6 +27,11 @@ static constexpr int UNWRAP_MAX_ROWS = 1024;      // rows per band = threads per
 // k = trunc(x / m) is found from x * (1/m) -- off by at most one (relative error ~2^-52 on a quotient < 2^38) -- and corrected by
 // the sign of the remainder; with the right k, fma(-k, m, x) is the exact remainder rounded once, i.e. the remainder itself.
 // Larger and non-finite arguments go to the library fmod.
+// Only the corrections towards zero can happen: the double 1.0 / m lies ABOVE the exact reciprocal of the double m (their
+// product exceeds 1 by 2.3e-17), so for x >= 0 the rounded product x * (1/m) is never below floor(x / m) (an integer
+// < 2^38, representable; rounding is monotonic) and k is the true quotient or one more: r lies in (-m, m), never r >= m; the
+// same mirrored for x < 0.  The two branches `r >= m` / `r <= -m` are kept as a guard and are dead for every double
+// (tests/test_unwrap_cpu.py takes the census of the branches on the probes of tests/test_gpu_unwrap_limits.py).
 __host__ __device__ __forceinline__ double unwrap_fmod_2pi(double x)
 {
 #pragma clang fp contract(off)

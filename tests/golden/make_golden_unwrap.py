@@ -14,7 +14,7 @@ process and calls from a FRESH thread (its own malloc arena); a case whose child
 surviving output is asserted bit-identical to ``tests/_unwrap_ref.py`` before it is written.
 
 Writes ``unwrap_cases.npz`` (small cases: input and output), ``unwrap_cases.json`` (every case: recipe, tau, sha256 of input and
-output; the two full frames by sha256 only) and ``unwrap_errors.json`` (the exceptions of the checks).
+output; the full frames and the widest maps by sha256 only) and ``unwrap_errors.json`` (the exceptions of the checks).
 
 Inputs use only ``+ * fmod`` on dyadic coefficients and an explicit integer hash (no sin, no numpy generator streams), so
 ``phase_input(recipe)`` rebuilds them bit for bit anywhere.
@@ -68,6 +68,12 @@ def sha(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
+def sha_canonical_nan(a):
+    a = np.array(a, dtype=np.float64)
+    a[np.isnan(a)] = np.nan
+    return sha(a)
+
+
 def _recipe(h, w, seed, ax=0.4375, ay=0.3125, axy=0.0, noise=0.5, wrap=1, special=0):
     return dict(h=h, w=w, seed=seed, ax=ax, ay=ay, axy=axy, noise=noise, wrap=wrap, special=special)
 
@@ -89,6 +95,10 @@ CASES.append(("big_t1", _recipe(20, 30, 81, ax=-263.0, ay=171.75, noise=2.0 ** 1
 CASES.append(("special", _recipe(40, 64, 90, special=1), 0.8, True))
 CASES.append(("frame1080", _recipe(1080, 1920, 100, ax=0.0859375, ay=0.03125, axy=2.0 ** -12), 0.8, False))
 CASES.append(("frame2160", _recipe(2160, 4096, 101, ax=0.0703125, ay=-0.046875, axy=2.0 ** -13), 1.0, False))
+# the kernel's widest map with its tallest band (LDS line of 16384 doubles + 2 x 1024 exchange slots = 147456 bytes), and a
+# wide map with NaN / +-inf (a line of 12000 doubles: above 64 KiB; two bands of rows when the band height is capped at 64)
+CASES.append(("frame_wide16384", _recipe(1024, 16384, 102, ax=0.0390625, ay=0.0546875, axy=2.0 ** -14), 0.8, False))
+CASES.append(("frame_wide_special", _recipe(70, 12000, 103, ax=0.0703125, ay=0.3125, special=1), 0.8, False))
 
 _CHILD = r"""
 import sys, threading, importlib.util, numpy as np
@@ -152,6 +162,10 @@ def main(modpath):
         ref = _unwrap_ref.unwrap(ph, tau)
         assert _unwrap_ref.identical(out, ref), name
         meta[name] = dict(recipe=recipe, tau=tau, whole=whole, input_sha256=sha(ph), output_sha256=sha(out))
+        if not whole and np.isnan(out).any():
+            # NaN sign and payload are the processor's business (x86 makes inf - inf a negative NaN): a map stored by hash
+            # alone also gets the hash of its output with every NaN replaced by numpy's
+            meta[name]["output_sha256_canonical_nan"] = sha_canonical_nan(out)
         if whole:
             arrays[name + "__in"] = ph
             arrays[name + "__out"] = out

@@ -54,3 +54,23 @@ def test_get3DPoints_matches_reprojectImageTo3D():
     want = pins["points"]
     ok = np.isfinite(want).all(-1)
     assert np.allclose(got[ok], want[ok], rtol=2e-6, atol=1e-6)
+
+
+def test_remap_coordinates_outside_every_range_match_cv2():
+    """NaN, +-inf, +-1e30, +-2^31, +-2^26 in mapx, mapy or both: the border value 0 (cvRound gives INT_MIN), and coordinates
+    on the 1/64-pixel grid, where cvRound's half-to-even decides the 1/32 cell -- the cases of
+    tests/test_gpu_rigs_limits.py and tests/test_rigs_cpu.py, against cv2.remap itself"""
+    cv2 = pytest.importorskip("cv2", reason="cv2 absent: the out-of-range semantics stay pinned to the published arithmetic only")
+    from simplestereo_amd import _rigs
+    rng = np.random.default_rng(4)
+    img = rng.integers(1, 256, (7, 8, 3)).astype(np.uint8)
+    out = [np.nan, np.inf, -np.inf, 1e30, -1e30, 2.0 ** 31, -2.0 ** 31, 2.0 ** 26, -2.0 ** 26]
+    mx = np.array([out + [2.25] * len(out) + out + [0.0] * len(out) + out], np.float32)
+    my = np.array([[3.5] * len(out) + out + out + out + [0.0] * len(out)], np.float32)
+    k = np.arange(-3 * 64, 10 * 64 + 1, dtype=np.float32) / np.float32(64)
+    gx, gy = np.meshgrid(k[::3], k[::5])
+    for ax, ay in ((mx, my), (np.ascontiguousarray(gx, np.float32), np.ascontiguousarray(gy, np.float32))):
+        for ours, theirs in ((_rigs.INTER_LINEAR, cv2.INTER_LINEAR), (_rigs.INTER_NEAREST, cv2.INTER_NEAREST)):
+            want = cv2.remap(img, ax, ay, theirs, borderMode=cv2.BORDER_CONSTANT, borderValue=0)
+            with np.errstate(invalid="ignore"):
+                assert np.array_equal(_rigs._remap(img, ax, ay, ours), want)

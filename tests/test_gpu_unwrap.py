@@ -48,7 +48,10 @@ def test_full_frame_goldens(uw, name):
     ph = make_golden_unwrap.phase_input(c["recipe"])
     assert make_golden_unwrap.sha(ph) == c["input_sha256"]
     out = uw.infiniteImpulseResponse(ph, c["tau"])
-    assert make_golden_unwrap.sha(out) == c["output_sha256"]
+    if "output_sha256_canonical_nan" in c:         # a map with NaN: sign and payload of a NaN are the processor's
+        assert make_golden_unwrap.sha_canonical_nan(out) == c["output_sha256_canonical_nan"]
+    else:
+        assert not np.isnan(out).any() and make_golden_unwrap.sha(out) == c["output_sha256"]
 
 
 def _random_map(rng, h, w, special):

@@ -222,3 +222,95 @@ def test_adimensional_points_geometry():
     # centre pixel maps to x = y = 0; depth = -f*b/d with f = width, b = 1
     assert np.allclose(p[3, 4], [0.0, 0.0, -8 / 2.0])
     assert np.allclose(p[..., 2], -4.0)
+
+
+# ---- the test references of oracle/rig_oracle.py themselves (what tests/test_gpu_rigs_limits.py holds the kernels to)
+def _fp64_reproject(d, Q):
+    """plain fp64 evaluation in the kernel's order of operations (no contraction), one division per component"""
+    H, W = d.shape
+    y, x = np.mgrid[0:H, 0:W].astype(np.float64)
+    v = [x, y, d.astype(np.float64), np.ones_like(x)]
+    p = [Q[r, 0] * v[0] + Q[r, 1] * v[1] + Q[r, 2] * v[2] + Q[r, 3] for r in range(4)]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.stack([p[0] / p[3], p[1] / p[3], p[2] / p[3]], -1).astype(np.float32)
+
+
+def test_reprojection_references_agree_and_bound_has_teeth():
+    """exact rational and longdouble references agree; plain fp64 evaluation lies within the derived bound
+    0.5 ulp32(t) + |t| 8 2^-53 (kX + kW); a value two float32 ulps away does not; W = 0 demands the class"""
+    from oracle import rig_oracle
+    rig = ss.RectifiedStereoRig.fromFile(RIGRECT)
+    rig.computeRectificationMaps(destDims=(640, 360))
+    rng = np.random.default_rng(12)
+    dense = rng.uniform(0.25, 2.0, (4, 4)) * rng.choice([-1.0, 1.0], (4, 4))
+    wzero = np.array([[1, 0, 0, -5.0], [0, 1, 0, -1.0], [0, 0, 0, 1000.0], [0, 0, 8.0, -8.0 * 37]])
+    for Q in (rig.getQ(), dense, wzero):
+        d = rng.integers(-32768, 32768, (3, 200)).astype(np.int16)
+        d[:, ::9] = 37
+        d[:, 5] = 37
+        d[0, :4] = (0, -1, -32768, 32767)
+        g = _fp64_reproject(d, Q)
+        assert rig_oracle.reproject_check_longdouble(g, d, Q)[0] == 0
+        t, tol, cls = rig_oracle.reproject_longdouble(d, Q)
+        for y in range(3):
+            for x in range(0, 200, 3):
+                assert rig_oracle.reproject_check_exact(g[y, x], Q, x, y, int(d[y, x])) is None
+                for r, e in enumerate(rig_oracle.reproject_exact(Q, x, y, int(d[y, x]))):
+                    if e[0] == "value":
+                        assert cls[y, x, r] == 0 and abs(float(t[y, x, r]) - float(e[1])) <= 1e-15 * abs(float(e[1])) + 1e-300
+                        # (the longdouble bound adds that evaluation's own error: 2^-11 of the second term)
+                        assert float(e[2]) * (1 - 1e-12) <= float(tol[y, x, r]) <= float(e[2]) * (1 + 2.0 ** -11 + 1e-12)
+                    else:
+                        assert cls[y, x, r] == (2 if e[0] == "nan" else e[1])
+        # teeth: two float32 ulps off is outside the bound (well-conditioned pixels), in both references
+        fin = np.argwhere(np.isfinite(g).all(-1) & (cls == 0).all(-1) & (tol[..., 0] <= np.spacing(np.abs(g[..., 0])) * 0.75))
+        assert len(fin) > 50
+        y, x = fin[7]
+        bad = g.copy()
+        bad[y, x, 0] = np.nextafter(np.nextafter(bad[y, x, 0], np.float32(np.inf)), np.float32(np.inf))
+        assert rig_oracle.reproject_check_longdouble(bad, d, Q)[0] == 1
+        assert rig_oracle.reproject_check_exact(bad[y, x], Q, x, y, int(d[y, x])) is not None
+    # W = 0 exactly (last matrix): +inf / -inf by the numerator's sign, NaN where that is 0 as well; a finite value or the wrong sign fails
+    assert [e[0] for e in rig_oracle.reproject_exact(wzero, 5, 1, 37)] == ["nan", "nan", "inf"]
+    assert rig_oracle.reproject_exact(wzero, 3, 2, 37) == [("inf", -1), ("inf", 1), ("inf", 1)]
+    assert rig_oracle.reproject_check_exact(np.float32([-np.inf, np.inf, np.inf]), wzero, 3, 2, 37) is None
+    assert rig_oracle.reproject_check_exact(np.float32([np.inf, np.inf, np.inf]), wzero, 3, 2, 37) is not None
+    assert rig_oracle.reproject_check_exact(np.float32([-3e38, np.inf, np.inf]), wzero, 3, 2, 37) is not None
+    assert rig_oracle.reproject_check_exact(np.float32([np.nan, np.inf, np.inf]), wzero, 3, 2, 37) is not None
+    # beyond the float32 range: infinity of the right sign
+    huge = np.array([[1e30, 0, 0, 1e30], [0, 1, 0, 0], [0, 0, 0, 1], [0, 0, 0, 1e-10]])
+    assert rig_oracle.reproject_exact(huge, 3, 2, 1)[0] == ("inf", 1)
+
+
+def test_remap_coordinates_outside_every_range_give_the_border_value():
+    """NaN, +-inf and coordinates whose product with 32 leaves int32: cvRound gives INT_MIN, the pixel is the border value 0 --
+    in the oracle's definition and in the numpy host path, bilinear and nearest"""
+    from oracle import rig_oracle
+    assert rig_oracle.cv_round(float("nan")) == rig_oracle.cv_round(float("inf")) == rig_oracle.cv_round(2.0 ** 31) == -2 ** 31
+    assert rig_oracle.cv_round(-2.0 ** 31) == -2 ** 31 and rig_oracle.cv_round(2.0 ** 31 - 1) == 2 ** 31 - 1
+    assert [rig_oracle.cv_round(v) for v in (0.5, 1.5, 2.5, -0.5, -1.5, -2.5)] == [0, 2, 2, 0, -2, -2]
+    rng = np.random.default_rng(4)
+    img = rng.integers(1, 256, (7, 8, 3)).astype(np.uint8)
+    out = [np.nan, np.inf, -np.inf, 1e30, -1e30, 2.0 ** 31, -2.0 ** 31, 2.0 ** 26, -2.0 ** 26]
+    mx = np.array([out + [2.25] * len(out) + out + [0.0] * len(out) + out], np.float32)
+    my = np.array([[3.5] * len(out) + out + out + out + [0.0] * len(out)], np.float32)
+    for interp in (_rigs.INTER_LINEAR, _rigs.INTER_NEAREST):
+        with np.errstate(invalid="ignore"):
+            host = _rigs._remap(img, mx, my, interp)
+        assert (host == 0).all()
+        assert np.array_equal(host, rig_oracle.remap_bilinear(img, mx, my, nearest=(interp == _rigs.INTER_NEAREST)))
+
+
+def test_remap_coordinates_on_the_64th_pixel_grid_oracle_equals_host_path():
+    """-1/64 -> cell 0, fraction 0; -3/64 -> cell -1, fraction 30/32 (half to even), and the whole grid around a small image"""
+    from oracle import rig_oracle
+    rng = np.random.default_rng(6)
+    img = rng.integers(1, 256, (4, 5, 3)).astype(np.uint8)
+    k = np.arange(-3 * 64, 7 * 64 + 1, dtype=np.float32) / np.float32(64)
+    mx, my = np.meshgrid(k[::3], k[::5])
+    mx, my = np.ascontiguousarray(mx, np.float32), np.ascontiguousarray(my, np.float32)
+    for interp in (_rigs.INTER_LINEAR, _rigs.INTER_NEAREST):
+        assert np.array_equal(_rigs._remap(img, mx, my, interp), rig_oracle.remap_bilinear(img, mx, my, nearest=(interp == 0)))
+    two = _rigs._remap(img, np.array([[-1 / 64, -3 / 64]], np.float32), np.zeros((1, 2), np.float32))
+    assert np.array_equal(two[0, 0], img[0, 0])
+    assert np.array_equal(two[0, 1], (30 * 32 * img[0, 0].astype(np.int64) + 512) >> 10)

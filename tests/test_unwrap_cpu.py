@@ -111,3 +111,68 @@ def test_restatement_equals_reference_golden(name):
     else:
         out = _unwrap_ref.unwrap(make_golden_unwrap.phase_input(c["recipe"]), c["tau"])
     assert make_golden_unwrap.sha(out) == c["output_sha256"]
+
+
+# ---- the restated fmod of the kernel (unwrap_fmod_2pi), modelled on the host: tests/_unwrap_probes.py
+def test_reciprocal_of_two_pi_is_rounded_up():
+    """The double 1.0 / (2 pi) lies above the exact reciprocal of the double 2 pi: the reason why the quotient estimate is never
+    too small, i.e. why the `r >= m` (x >= 0) and `r <= -m` (x < 0) corrections of unwrap_fmod_2pi are dead for every double."""
+    from fractions import Fraction
+    import _unwrap_probes as P
+    assert Fraction(P.C) * Fraction(P.M) > 1
+    # the boundary cases of the argument: x = m * 2^j has the exact quotient 2^j, and the estimate finds it
+    for j in range(0, 38):                              # m * 2^38 is past the switch at 2^40
+        x = P.M * 2.0 ** j
+        assert int(x * P.C) == 2 ** j and P.branch(x) == "pos_direct" and P.branch(-x) == "neg_direct"
+
+
+def test_fmod_model_equals_fmod_and_probes_take_every_reachable_branch():
+    """The host-side model of unwrap_fmod_2pi (k from trunc(x * (1/m)), one exact fma, one correction) gives math.fmod's bits on
+    every argument that the probe maps of tests/test_gpu_unwrap_limits.py pass to it, and those arguments take every branch
+    that any double can take, both corrections towards zero for both signs included."""
+    import math
+    from fractions import Fraction
+    import _unwrap_probes as P
+    a = P.probes()
+    assert 1.5e5 < len(a) < 3e5 and np.array_equal(a, P.probes())          # deterministic
+    _, args = P.fmod_arguments(P.pair_maps(a), 1.0)
+    census = P.branch_census(args)
+    print("census", census)
+    assert sum(census.values()) == len(args)
+    for b in P.BRANCHES:
+        assert (census[b] == 0) if b in P.DEAD else (census[b] >= 100), (b, census)
+    # the prefilter of branch_census agrees with the exact model
+    sub = args[:: max(1, len(args) // 20000)]
+    exact = dict.fromkeys(P.BRANCHES, 0)
+    for v in sub.tolist():
+        exact[P.branch(v)] += 1
+    assert exact == P.branch_census(sub)
+
+    def fma(x, y, z):                                   # exact product and sum, rounded once
+        return float(Fraction(x) * Fraction(y) + Fraction(z))
+
+    def model(x):
+        k = float(math.trunc(x * P.C))
+        r = fma(-k, P.M, x)
+        if x >= 0:
+            if r < 0:
+                k -= 1
+            elif r >= P.M:
+                k += 1
+            else:
+                return r
+        else:
+            if r > 0:
+                k += 1
+            elif r <= -P.M:
+                k -= 1
+            else:
+                return r
+        return fma(-k, P.M, x)
+
+    fast = args[np.abs(args) < P.SWITCH]
+    near = fast[np.abs(fast - np.rint(fast * P.C) * P.M) < 1e-3]           # the arguments near a multiple of 2 pi ...
+    rng = np.random.default_rng(1)
+    for v in np.concatenate([near[:: max(1, len(near) // 20000)], rng.choice(fast, 5000)]).tolist():   # ... and a sample of the rest
+        got, want = model(v), math.fmod(v, P.M)
+        assert got == want and math.copysign(1, got) == math.copysign(1, want) or (want == 0 and got == 0), v
