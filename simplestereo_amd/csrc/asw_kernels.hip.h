@@ -116,7 +116,7 @@ struct AswArgs {
 // asw_aggregate_pipe_kernel<.., SLC, SRC, SEC> used to take only its three LDS strides as constants and read the other ~30 geometry
 // values from the kernel arguments: with the pointers and image sizes that is more scalars than the 102 SGPRs hold, and the compiler
 // spilled 76-155 of them into VGPR lanes (v_writelane / v_readlane).  The static instantiations now derive EVERYTHING from
-// (winSize, XG, DG, JC) at compile time -- a constexpr restatement of the pipe branch of asw_layout_e (ssamd_api.hip), which the
+// (winSize, XG, DG, JC) at compile time -- a constexpr restatement of the pipe branch of asw_layout_e (asw_plan.h), which the
 // launcher compares field by field with the geometry it planned before it picks a static instantiation (asw_pipe_geom_matches).
 struct AswPipeTileId { int win, XG, DG, JC; };
 __host__ __device__ constexpr int asw_cx_round_up(int v, int m) { return (v + m - 1) / m * m; }

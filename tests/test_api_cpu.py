@@ -148,7 +148,8 @@ def test_tuning_options_are_a_table_not_the_environment(ss):
     """the SSAMD_* hooks are read from the environment once, at load; afterwards only ssamd_set_option changes them
     (no getenv on the per-call host path) and unknown names are refused"""
     from simplestereo_amd import _native
-    src = open(os.path.join(ROOT, "simplestereo_amd", "csrc", "ssamd_api.hip")).read()
+    csrc = os.path.join(ROOT, "simplestereo_amd", "csrc")          # (every file: the option table lives in ssamd_options.h)
+    src = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h", ".inc")))
     assert src.count("getenv(") == 1            # tuning_from_env, run once by the static initialiser
     f0 = _native.asw_kernel_form(1920, 10, 35, 16, 0)
     assert f0["wave_kernel"] in (4, 8)
