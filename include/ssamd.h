@@ -13,6 +13,8 @@
  *                           called from StereoGSW.compute, passive.py:153-156
  *   ssamd_iir_unwrap   <->  _unwrapping.infiniteImpulseResponse   simplestereo/_unwrapping.cpp:50-156
  *                           called from unwrapping.infiniteImpulseResponse, unwrapping.py:10-41
+ *   ssamd_ftp_phase    <->  the demodulation of StereoFTP.getCloud   simplestereo/active.py:675-737
+ *                           (pure numpy in the reference: fft, band mask, ifft, angle; NOT the StereoFTP classes)
  *   ssamd_*_device     same operators on buffers already resident in HBM (no
  *                      reference counterpart: the reference has no device).
  *
@@ -39,7 +41,7 @@
 extern "C" {
 #endif
 
-#define SSAMD_ABI_VERSION 6      /* 6: ssamd_iir_unwrap / ssamd_iir_unwrap_device and profile slot SSAMD_K_UNWRAP; 5:ssamd_asw_exact_device_rows2 / _rectified_device (round 6: near-ties selected inside the aggregation kernels); 4: ssamd_asw_exact* (round 5); 3: GSW autotuning; 2: ssamd_set_option (round 3) + the multi-device and verification entry points added in round 2 */
+#define SSAMD_ABI_VERSION 7      /* 7: ssamd_ftp_phase / ssamd_ftp_phase_device / ssamd_ftp_band and profile slot SSAMD_K_FTP; 6: ssamd_iir_unwrap / ssamd_iir_unwrap_device and profile slot SSAMD_K_UNWRAP; 5:ssamd_asw_exact_device_rows2 / _rectified_device (round 6: near-ties selected inside the aggregation kernels); 4: ssamd_asw_exact* (round 5); 3: GSW autotuning; 2: ssamd_set_option (round 3) + the multi-device and verification entry points added in round 2 */
 
 #define SSAMD_OK 0
 #define SSAMD_EINVAL (-1)     /* bad argument (message tells which)            */
@@ -246,6 +248,33 @@ int ssamd_reproject_device(const int16_t *d_disparity, int h, int w, const doubl
 int ssamd_iir_unwrap(const double *phase, int n, int h, int w, double tau, double *out, int device);
 int ssamd_iir_unwrap_device(const double *d_phase, int n, int h, int w, double tau, double *d_out, void *stream);
 
+/* ---- Fourier-transform profilometry: wrapped phase of a fringe image against a reference image ---------------- */
+/* The demodulation step of the reference's FTP pipeline (StereoFTP.getCloud, active.py:675-737; StereoFTP_PhaseOnly.getPhase,
+ * :2012-2074), which is pure numpy there: gray = channel maximum (convertGrayscale), np.fft.fft along x of both images, the
+ * per-row band mask, np.fft.ifft, np.angle(ghat * conj(g0hat)).  One HIP kernel (csrc/ftp_kernels.hip.h): a band-limited direct
+ * DFT in fp64, one workgroup per row, any width 1 .. 8192 (SSAMD_ELIMIT above: the LDS layout); h is bounded by the grid only.
+ * Not bit-identical to numpy's pocketfft (another summation order): within a few ulp of pi of the exact angle wherever
+ * |ghat * conj(g0hat)| is not tiny against its row.
+ *   img_obj / img_ref : uint8, C-contiguous [h][w] (ch = 1) or [h][w][3] (ch = 3, B,G,R; reduced by the channel maximum);
+ *                       the two channel counts may differ.
+ *   fmin, fmax        : HOST arrays of h doubles, the pass band of each row in cycles per pixel (the reference's
+ *                       fc - radius_factor * fc and fc + radius_factor * fc).  Bin s (signed, -(w/2) .. (w-1)/2) of frequency
+ *                       f(s) = (double)s * (1.0 / (double)w) -- np.fft.fftfreq's two roundings -- is kept iff
+ *                       !(f(s) - fmin < 0) && !(f(s) - fmax > 0): a NaN bound masks nothing on its side.
+ *   out               : fp64 [h][w]: atan2(Im z, Re z), z = ghat * conj(g0hat); a row with an empty band is 0.0.
+ *   unwrap            : 0 the wrapped phase; 1 ssamd_iir_unwrap's kernel runs on it (tau; same stream, no host round trip) and
+ *                       out is what ssamd_iir_unwrap gives on the wrapped map, bit for bit; the unwrapper's checks and limits apply.
+ * ssamd_ftp_phase: host buffers, synchronous (device as ssamd_iir_unwrap).  ssamd_ftp_phase_device: device image and output
+ * buffers (fmin / fmax stay host arrays and are consumed before the call returns), asynchronous on `stream`. */
+#define SSAMD_FTP_MAX_W 8192
+int ssamd_ftp_phase(const uint8_t *img_obj, int ch_obj, const uint8_t *img_ref, int ch_ref, int h, int w, const double *fmin,
+                    const double *fmax, int unwrap, double tau, double *out, int device);
+int ssamd_ftp_phase_device(const uint8_t *d_img_obj, int ch_obj, const uint8_t *d_img_ref, int ch_ref, int h, int w,
+                           const double *fmin, const double *fmax, int unwrap, double tau, double *d_out, void *stream);
+/* The band planner alone (csrc/ftp_plan.h; needs no device): slo[y] .. shi[y] = the kept signed bins of row y, one contiguous
+ * range, slo = 0, shi = -1 when none is kept. */
+int ssamd_ftp_band(int w, int h, const double *fmin, const double *fmax, int32_t *slo, int32_t *shi);
+
 /* ---- verification / measurement helpers ------------------------------------ */
 
 /* Raw left-referenced aggregated ASW costs, float32 [height][width][nD] with
@@ -302,7 +331,8 @@ int ssamd_debug_gsw_sqrt(int n, float *out);
 #define SSAMD_K_ASW_ALT 7    /* alternate-rows mode: bounded search on the odd rows */
 #define SSAMD_K_ASW_EXACT 8  /* fp64 tie-break pass of ssamd_asw_exact* (fp64 Lab, filter, winners, eval, resolve, patch) */
 #define SSAMD_K_UNWRAP 9     /* phase unwrapping wavefront (iir_unwrap_kernel)                                     */
-#define SSAMD_K_COUNT 10
+#define SSAMD_K_FTP 10       /* Fourier-profilometry wrapped phase (ftp_phase_kernel)                              */
+#define SSAMD_K_COUNT 11
 int ssamd_profile_enable(int on);
 int ssamd_profile_reset(void);
 int ssamd_profile_read(double *ms /*[SSAMD_K_COUNT]*/, long long *launches /*[SSAMD_K_COUNT]*/);

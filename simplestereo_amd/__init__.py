@@ -16,6 +16,7 @@ from ._rigs import StereoRig, RectifiedStereoRig
 from . import strips
 from . import points
 from . import unwrapping
+from . import active
 
 __version__ = "0.6.0"
-__all__ = ["passive", "StereoRig", "RectifiedStereoRig", "strips", "points", "unwrapping"]
+__all__ = ["passive", "StereoRig", "RectifiedStereoRig", "strips", "points", "unwrapping", "active"]

@@ -17,10 +17,10 @@ if os.environ.get("SSAMD_LIB"):
         raise ImportError("SSAMD_LIB is an experiment hook: set SSAMD_EXPERIMENT=1 as well to load %s instead of the product "
                           "library" % os.environ["SSAMD_LIB"])
     LIB_PATH = os.environ["SSAMD_LIB"]
-ABI_VERSION = 6
+ABI_VERSION = 7
 
-(K_LAB, K_ASW_AGG, K_ASW_FIN, K_GSW_AGG, K_GSW_FIN, K_REMAP, K_REPROJECT, K_ASW_ALT, K_ASW_EXACT, K_UNWRAP,
- K_COUNT) = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
+(K_LAB, K_ASW_AGG, K_ASW_FIN, K_GSW_AGG, K_GSW_FIN, K_REMAP, K_REPROJECT, K_ASW_ALT, K_ASW_EXACT, K_UNWRAP, K_FTP,
+ K_COUNT) = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11
 
 _lib = None
 _u8p = ctypes.c_void_p
@@ -111,6 +111,12 @@ def lib():
     L.ssamd_iir_unwrap.argtypes = [P, I, I, I, D, P, I]
     L.ssamd_iir_unwrap_device.restype = I
     L.ssamd_iir_unwrap_device.argtypes = [P, I, I, I, D, P, P]
+    L.ssamd_ftp_phase.restype = I
+    L.ssamd_ftp_phase.argtypes = [P, I, P, I, I, I, P, P, I, D, P, I]
+    L.ssamd_ftp_phase_device.restype = I
+    L.ssamd_ftp_phase_device.argtypes = [P, I, P, I, I, I, P, P, I, D, P, P]
+    L.ssamd_ftp_band.restype = I
+    L.ssamd_ftp_band.argtypes = [I, I, P, P, P, P]
     L.ssamd_debug_exact_queue.restype = I
     L.ssamd_debug_exact_queue.argtypes = [I, ctypes.c_longlong, P, P, P]
     L.ssamd_debug_libm.restype = I

@@ -40,6 +40,7 @@ namespace ssamd {
 #include "asw_exact_kernels.hip.h"
 #include "rig_kernels.hip.h"
 #include "unwrap_kernels.hip.h"
+#include "ftp_kernels.hip.h"
 
 using namespace ssamd;
 
@@ -65,6 +66,7 @@ int fail(int code, const char *fmt, ...)
 #include "ssamd_options.h"
 #include "asw_plan.h"
 #include "gsw_plan.h"
+#include "ftp_plan.h"
 
 // Experiment / test hooks (declared in ssamd_options.h).  The SSAMD_* environment variables are read ONCE, when
 // the library is loaded; afterwards the table only changes through ssamd_set_option (tests, tools).  The host path of an operator
@@ -193,6 +195,11 @@ struct Ctx {
     DevBuf imgL, imgR, recL, recR, keyL, keyR, disp, costs, lab, altq, evol, altdisp;
     DevBuf xlabL, xlabR, xflags, xqueue, xcost, xslots, xctr, xraw, xwtab;      // fp64 tie-break pass (asw_exact_kernels.hip.h)
     DevBuf uwIn, uwOut;                 // host-buffer phase unwrapping (unwrap_kernels.hip.h)
+    DevBuf ftpBand, ftpPhase;           // FTP phase (ftp_kernels.hip.h): kept bins per row; the wrapped map on its way to the unwrapper
+    std::map<int, DevBuf> ftpTabs;      // twiddle table e^{2 pi i j / w} per width, built on the device
+    int32_t *ftpBandHost = nullptr;     // pinned staging of the bands: the asynchronous upload reads it after the call returned
+    size_t ftpBandHostCap = 0;          // ... in int32 pairs
+    hipEvent_t ftp_band_copied = nullptr;   // recorded behind that upload; the next call waits for it before it refills the staging
     unsigned int xcap = 0, xrawcap = 0; // queue capacities of the last exact call
     TableCache proxTabs{8}, gswTabs{4}, proxTabs64{8};
     std::map<const void *, int> max_dyn_lds;   // hipFuncAttributeMaxDynamicSharedMemorySize already granted per kernel
@@ -1494,7 +1501,7 @@ const char *ssamd_kernel_name(int slot)
                                                "asw finalize (wta_decode / lr_check_fill)",
                                                "gsw_aggregate_kernel", "gsw finalize (lr_check_fill)", "remap_bgr_kernel", "reproject_kernel",
                                                "asw_alt_fill_kernel", "asw fp64 tie-break pass (bgr2lab_f64_pair + asw_exact_winners / _eval / _resolve / _patch kernels)",
-                                               "iir_unwrap_kernel"};
+                                               "iir_unwrap_kernel", "ftp_phase_kernel"};
     return (slot >= 0 && slot < SSAMD_K_COUNT) ? names[slot] : "";
 }
 
@@ -1922,6 +1929,133 @@ int ssamd_iir_unwrap_device(const double *d_phase, int n, int h, int w, double t
     CtxLock c;
     if ((rc = get_ctx(-1, c))) return rc;
     return unwrap_launch(*c, d_phase, n, h, w, tau, d_out, (hipStream_t)stream);
+}
+
+namespace {
+// band planning, table and launches of ssamd_ftp_phase*; the caller holds the context and has ordered the scratch (ScratchOrder)
+static_assert(FTP_MAX_W == SSAMD_FTP_MAX_W, "ssamd.h states the width limit of ftp_plan.h");
+int ftp_check(int ch_obj, int ch_ref, int h, int w, const double *fmin, const double *fmax, int unwrap, double tau)
+{
+    if (h <= 0 || w <= 0) return fail(SSAMD_EINVAL, "Wrong image dimensions!");
+    if ((ch_obj != 1 && ch_obj != 3) || (ch_ref != 1 && ch_ref != 3)) return fail(SSAMD_EINVAL, "images must have 1 or 3 channels");
+    if (!fmin || !fmax) return fail(SSAMD_EINVAL, "NULL band bounds");
+    if (unwrap != 0 && unwrap != 1) return fail(SSAMD_EINVAL, "unwrap must be 0 or 1");
+    if (w > FTP_MAX_W) return fail(SSAMD_ELIMIT, "rows wider than %d columns are not supported (width %d)", FTP_MAX_W, w);
+    return unwrap ? unwrap_check(1, h, w, tau) : SSAMD_OK;
+}
+
+int ftp_twiddles(Ctx &c, int w, hipStream_t s, const double2 **tw)
+{
+    auto it = c.ftpTabs.find(w);
+    if (it == c.ftpTabs.end()) {
+        if (c.ftpTabs.size() >= 16) {                    // hipFree waits for the kernels that may still read a table
+            for (auto &e : c.ftpTabs) e.second.release();
+            c.ftpTabs.clear();
+        }
+        DevBuf buf;
+        int rc = buf.reserve((size_t)w * sizeof(double2));
+        if (rc) return rc;
+        hipLaunchKernelGGL(ftp_twiddle_kernel, dim3((w + 255) / 256), dim3(256), 0, s, (double2 *)buf.ptr, w);
+        HIP_TRY(hipGetLastError());
+        it = c.ftpTabs.emplace(w, buf).first;
+    }
+    *tw = (const double2 *)it->second.ptr;
+    return SSAMD_OK;
+}
+
+int ftp_launch(Ctx &c, const uint8_t *d_obj, int ch_obj, const uint8_t *d_ref, int ch_ref, int h, int w, const double *fmin,
+               const double *fmax, int unwrap, double tau, double *d_out, hipStream_t s)
+{
+    int rc;
+    // the bands go through pinned staging that the previous call's upload may still be reading
+    if (!c.ftp_band_copied) HIP_TRY(hipEventCreateWithFlags(&c.ftp_band_copied, hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(c.ftp_band_copied));
+    if ((size_t)h > c.ftpBandHostCap) {
+        if (c.ftpBandHost) { (void)hipHostFree(c.ftpBandHost); c.ftpBandHost = nullptr; c.ftpBandHostCap = 0; }
+        const size_t want = (size_t)h + (size_t)h / 8 + 64;
+        HIP_TRY(hipHostMalloc((void **)&c.ftpBandHost, want * 2 * sizeof(int32_t), hipHostMallocDefault));
+        c.ftpBandHostCap = want;
+    }
+    int max_bins = 0;
+    for (int y = 0; y < h; ++y) {
+        int32_t lo, hi;
+        ftp_band_row(w, fmin[y], fmax[y], lo, hi);
+        c.ftpBandHost[2 * (size_t)y] = lo;
+        c.ftpBandHost[2 * (size_t)y + 1] = hi;
+        max_bins = std::max(max_bins, hi - lo + 1);
+    }
+    if ((rc = c.ftpBand.reserve((size_t)h * 2 * sizeof(int32_t)))) return rc;
+    HIP_TRY(hipMemcpyAsync(c.ftpBand.ptr, c.ftpBandHost, (size_t)h * 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(c.ftp_band_copied, s));
+    const double2 *tw = nullptr;
+    if ((rc = ftp_twiddles(c, w, s, &tw))) return rc;
+    double *d_phase = d_out;
+    if (unwrap) {
+        if ((rc = c.ftpPhase.reserve((size_t)h * w * sizeof(double)))) return rc;
+        d_phase = (double *)c.ftpPhase.ptr;
+    }
+    const FtpGeom g = ftp_geometry(w);
+    const int q = ftp_lanes_per_bin(g.threads, std::max(max_bins, 1));
+    auto launch = [&](auto kernel) -> int {
+        int r = grant_dyn_lds(c, reinterpret_cast<const void *>(kernel), g.lds_bytes);
+        if (r) return r;
+        Timed t(c, s, SSAMD_K_FTP);
+        hipLaunchKernelGGL(kernel, dim3(h), dim3(g.threads), g.lds_bytes, s, d_obj, ch_obj, d_ref, ch_ref, w,
+                           (const int2 *)c.ftpBand.ptr, tw, q, FTP_BIN_CHUNK, d_phase);
+        HIP_TRY(hipGetLastError());
+        return SSAMD_OK;
+    };
+    switch (g.cpt) {
+    case 1: rc = launch(&ftp_phase_kernel<1>); break;
+    case 2: rc = launch(&ftp_phase_kernel<2>); break;
+    case 4: rc = launch(&ftp_phase_kernel<4>); break;
+    default: rc = launch(&ftp_phase_kernel<8>); break;
+    }
+    if (rc) return rc;
+    return unwrap ? unwrap_launch(c, d_phase, 1, h, w, tau, d_out, s) : SSAMD_OK;
+}
+}  // namespace
+
+int ssamd_ftp_band(int w, int h, const double *fmin, const double *fmax, int32_t *slo, int32_t *shi)
+{
+    if (w <= 0 || h < 0) return fail(SSAMD_EINVAL, "Wrong image dimensions!");
+    if (h > 0 && (!fmin || !fmax || !slo || !shi)) return fail(SSAMD_EINVAL, "NULL buffer");
+    for (int y = 0; y < h; ++y) ftp_band_row(w, fmin[y], fmax[y], slo[y], shi[y]);
+    return SSAMD_OK;
+}
+
+int ssamd_ftp_phase(const uint8_t *img_obj, int ch_obj, const uint8_t *img_ref, int ch_ref, int h, int w, const double *fmin,
+                    const double *fmax, int unwrap, double tau, double *out, int device)
+{
+    if (!img_obj || !img_ref || !out) return fail(SSAMD_EINVAL, "NULL buffer");
+    int rc = ftp_check(ch_obj, ch_ref, h, w, fmin, fmax, unwrap, tau);
+    if (rc) return rc;
+    CtxLock c;
+    if ((rc = get_ctx(device, c))) return rc;
+    const size_t px = (size_t)h * w, bytes = px * sizeof(double);
+    if ((rc = c->imgL.reserve(px * ch_obj)) || (rc = c->imgR.reserve(px * ch_ref)) || (rc = c->uwOut.reserve(bytes))) return rc;
+    hipStream_t s = c->stream;
+    ScratchOrder order(*c, s);
+    HIP_TRY(hipMemcpyAsync(c->imgL.ptr, img_obj, px * ch_obj, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->imgR.ptr, img_ref, px * ch_ref, hipMemcpyHostToDevice, s));
+    if ((rc = ftp_launch(*c, (const uint8_t *)c->imgL.ptr, ch_obj, (const uint8_t *)c->imgR.ptr, ch_ref, h, w, fmin, fmax, unwrap, tau,
+                         (double *)c->uwOut.ptr, s)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(out, c->uwOut.ptr, bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return SSAMD_OK;
+}
+
+int ssamd_ftp_phase_device(const uint8_t *d_img_obj, int ch_obj, const uint8_t *d_img_ref, int ch_ref, int h, int w,
+                           const double *fmin, const double *fmax, int unwrap, double tau, double *d_out, void *stream)
+{
+    if (!d_img_obj || !d_img_ref || !d_out) return fail(SSAMD_EINVAL, "NULL buffer");
+    int rc = ftp_check(ch_obj, ch_ref, h, w, fmin, fmax, unwrap, tau);
+    if (rc) return rc;
+    CtxLock c;
+    if ((rc = get_ctx(-1, c))) return rc;
+    ScratchOrder order(*c, (hipStream_t)stream);        // the band, the table and the wrapped map are the context's
+    return ftp_launch(*c, d_img_obj, ch_obj, d_img_ref, ch_ref, h, w, fmin, fmax, unwrap, tau, d_out, (hipStream_t)stream);
 }
 
 namespace {
