@@ -574,87 +574,20 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(
         }
     }
 
-    // ---- weighted average (_passive.cpp:88) and the two WTA reductions (as asw_aggregate_kernel)
+    // ---- weighted average (_passive.cpp:88), the two WTA reductions, near-tie selection, outputs: asw_epilogue.inc
     int tidf = threadIdx.x;
     asm volatile("" : "+v"(tidf));
-    AswKeyTile<RX, ASW_RD> kt;                      // cost images of the register tile (exact mode re-reads them after the barrier)
-    if (tidf < nact) {
-        const int xg = pk_xd & 0xffff, dg = pk_xd >> 16;
-        u64 diag[RX + ASW_RD - 1];
-#pragma unroll
-        for (int k = 0; k < RX + ASW_RD - 1; ++k) diag[k] = KEY_NONE;
-#pragma unroll
-        for (int xi = 0; xi < RX; ++xi) {
-            const int x = x0 + RX * xg + xi;
-            u64 bl = KEY_NONE;
-#pragma unroll
-            for (int di = 0; di < ASW_RD; ++di) {
-                const int d = dlo + ASW_RD * dg + di;
-                const bool valid = (x < W) && (d <= A.maxD) && (x - d >= 0);
-                kt.v[xi][di] = 0xffffffffu;
-                if (valid) {
-                    float c;
-                    const u64 hi = (u64)asw_cost_key(accN[xi][di], accS[xi][di], c) << 32;
-                    kt.v[xi][di] = (uint32_t)(hi >> 32);
-                    bl = min(bl, hi | (u64)(uint32_t)d);
-                    diag[xi - di + ASW_RD - 1] = min(diag[xi - di + ASW_RD - 1], hi | (u64)(uint32_t)x);
-                    if (WITH_COSTS)
-                        A.costs[((size_t)(y - A.row0) * W + x) * (A.maxD - A.minD + 1) + (d - A.minD)] = A.cost_keys ? __uint_as_float((uint32_t)(hi >> 32)) : c;
-                }
-            }
-            if (bl != KEY_NONE) atomicMin(&bestL[RX * xg + xi], bl);
-        }
-        if (A.keyR) {
-            const int base = RX * xg - ASW_RD * dg + Dc - ASW_RD;
-#pragma unroll
-            for (int k = 0; k < RX + ASW_RD - 1; ++k)
-                if (diag[k] != KEY_NONE) atomicMin(&bestR[base + k], diag[k]);
-        }
-    }
-    __syncthreads();
-    const size_t orow = (size_t)(y - A.row0) * W;
-    const bool xq = !WITH_COSTS && A.xq.entries != nullptr;          // exact mode: near-ties of the winners go to the fp64 pass's queue
-    if (xq) {
-        const int xg = pk_xd & 0xffff, dg = pk_xd >> 16;
-        asw_exact_select<RX, ASW_RD>(A.xq, tidf < nact, kt, bestL + RX * xg, A.keyR ? bestR + (RX * xg - ASW_RD * dg + Dc - ASW_RD) : nullptr,
-                                     x0 + RX * xg, dlo + ASW_RD * dg, (uint32_t)orow, exact_zkey(win));
-    }
-    if (A.disp) {
-        for (int k = tid; k < Tx; k += nthr) {
-            const int x = x0 + k;
-            if (x < W) A.disp[orow + x] = bestL[k] == KEY_NONE ? (int16_t)x : (int16_t)(uint32_t)bestL[k];
-        }
-        return;
-    }
-    if (xq) {
-        // tile-local winners meet the pixels' running minima: the loser of each meeting is queued if it is a near-tie (uniform trip counts)
-        for (int k0 = 0; k0 < Tx; k0 += nthr) {
-            const int k = k0 + tid, x = x0 + k;
-            const bool have = k < Tx && x < W && bestL[k < Tx ? k : 0] != KEY_NONE;
-            const u64 mine = have ? bestL[k] : KEY_NONE;
-            const u64 old = have ? atomicMin(&A.keyL[orow + x], mine) : KEY_NONE;
-            asw_exact_merge<false>(A.xq, have, mine, old, (uint32_t)orow, x, exact_zkey(win));
-        }
-        if (A.keyR)
-            for (int k0 = 0; k0 < nRc; k0 += nthr) {
-                const int k = k0 + tid, xr = xrc_lo + k;
-                const bool have = k < nRc && (unsigned)xr < (unsigned)W && bestR[k < nRc ? k : 0] != KEY_NONE;
-                const u64 mine = have ? bestR[k] : KEY_NONE;
-                const u64 old = have ? atomicMin(&A.keyR[orow + xr], mine) : KEY_NONE;
-                asw_exact_merge<true>(A.xq, have, mine, old, (uint32_t)orow, xr, exact_zkey(win));
-            }
-        return;
-    }
-    for (int k = tid; k < Tx; k += nthr) {
-        const int x = x0 + k;
-        if (x < W && bestL[k] != KEY_NONE) atomicMin(&A.keyL[orow + x], bestL[k]);
-    }
-    if (A.keyR) {
-        for (int k = tid; k < nRc; k += nthr) {
-            const int xr = xrc_lo + k;
-            if ((unsigned)xr < (unsigned)W && bestR[k] != KEY_NONE) atomicMin(&A.keyR[orow + xr], bestR[k]);
-        }
-    }
+#define ASW_EPI_RD ASW_RD
+#define ASW_EPI_LIVE (tidf < nact)
+#define ASW_EPI_XG(live) (pk_xd & 0xffff)
+#define ASW_EPI_DG(live) (pk_xd >> 16)
+#define ASW_EPI_TX Tx
+#define ASW_EPI_NRC nRc
+#define ASW_EPI_TID tid
+#define ASW_EPI_NTHR nthr
+#define ASW_EPI_SYNC() __syncthreads()
+#define ASW_EPI_ROW (size_t)(y - A.row0) * W
+#include "asw_epilogue.inc"
 }
 
 }  // namespace ssamd

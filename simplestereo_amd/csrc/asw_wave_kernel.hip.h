@@ -426,85 +426,23 @@ __global__ __launch_bounds__(256, RX == 8 ? SSAMD_WAVE8_OCC : SSAMD_WAVE4_OCC) v
         }
     }
 
-    // ---- weighted average (_passive.cpp:88) and the two winner-take-all reductions, inside the wave
+    // ---- weighted average (_passive.cpp:88), the two winner-take-all reductions (inside the wave), near-tie selection, outputs:
+    //      asw_epilogue.inc, after bestL / bestR are cleared
     asw_wave_sync();
     for (int k = lane; k < Txw; k += 64) bestL[k] = KEY_NONE;        // (these share the pixel rows' space)
     for (int k = lane; k <= nRcw; k += 64) bestR[k] = KEY_NONE;
     asw_wave_sync();
-    AswKeyTile<RX, ASW_RD> kt;                      // cost images of the register tile (exact mode re-reads them after the wave's barrier)
-    if (active) {
-        u64 diag[RX + ASW_RD - 1];
-#pragma unroll
-        for (int k = 0; k < RX + ASW_RD - 1; ++k) diag[k] = KEY_NONE;
-#pragma unroll
-        for (int xi = 0; xi < RX; ++xi) {
-            const int x = x0 + RX * xg + xi;
-            u64 bl = KEY_NONE;
-#pragma unroll
-            for (int di = 0; di < ASW_RD; ++di) {
-                const int d = dlo + ASW_RD * dg + di;
-                const bool valid = (x < W) && (d <= A.maxD) && (x - d >= 0);
-                kt.v[xi][di] = 0xffffffffu;
-                if (valid) {
-                    float c;
-                    const u64 hi = (u64)asw_cost_key(accN[xi][di], accS[xi][di], c) << 32;
-                    kt.v[xi][di] = (uint32_t)(hi >> 32);
-                    bl = min(bl, hi | (u64)(uint32_t)d);
-                    diag[xi - di + ASW_RD - 1] = min(diag[xi - di + ASW_RD - 1], hi | (u64)(uint32_t)x);
-                    if (WITH_COSTS)
-                        A.costs[(orow + x) * (A.maxD - A.minD + 1) + (d - A.minD)] = A.cost_keys ? __uint_as_float((uint32_t)(hi >> 32)) : c;
-                }
-            }
-            if (bl != KEY_NONE) atomicMin(&bestL[RX * xg + xi], bl);
-        }
-        if (A.keyR) {
-            const int base = RX * xg - ASW_RD * dg + Dc - ASW_RD;
-#pragma unroll
-            for (int k = 0; k < RX + ASW_RD - 1; ++k)
-                if (diag[k] != KEY_NONE) atomicMin(&bestR[base + k], diag[k]);
-        }
-    }
-    asw_wave_sync();
-    const bool xq = !WITH_COSTS && A.xq.entries != nullptr;          // exact mode: near-ties of the winners go to the fp64 pass's queue
-    if (xq)
-        asw_exact_select<RX, ASW_RD>(A.xq, active, kt, bestL + RX * xg, A.keyR ? bestR + (RX * xg - ASW_RD * dg + Dc - ASW_RD) : nullptr,
-                                 x0 + RX * xg, dlo + ASW_RD * dg, (uint32_t)orow, exact_zkey(win));
-    if (A.disp) {
-        for (int k = lane; k < Txw; k += 64) {
-            const int x = x0 + k;
-            if (x < W) A.disp[orow + x] = bestL[k] == KEY_NONE ? (int16_t)x : (int16_t)(uint32_t)bestL[k];
-        }
-        return;
-    }
-    if (xq) {
-        // strip-local winners meet the pixels' running minima: the loser of each meeting is queued if it is a near-tie
-        for (int k0 = 0; k0 < Txw; k0 += 64) {
-            const int k = k0 + lane, x = x0 + k;
-            const bool have = k < Txw && x < W && bestL[k < Txw ? k : 0] != KEY_NONE;
-            const u64 mine = have ? bestL[k] : KEY_NONE;
-            const u64 old = have ? atomicMin(&A.keyL[orow + x], mine) : KEY_NONE;
-            asw_exact_merge<false>(A.xq, have, mine, old, (uint32_t)orow, x, exact_zkey(win));
-        }
-        if (A.keyR)
-            for (int k0 = 0; k0 < nRcw; k0 += 64) {
-                const int k = k0 + lane, xr = xrc_lo + k;
-                const bool have = k < nRcw && (unsigned)xr < (unsigned)W && bestR[k < nRcw ? k : 0] != KEY_NONE;
-                const u64 mine = have ? bestR[k] : KEY_NONE;
-                const u64 old = have ? atomicMin(&A.keyR[orow + xr], mine) : KEY_NONE;
-                asw_exact_merge<true>(A.xq, have, mine, old, (uint32_t)orow, xr, exact_zkey(win));
-            }
-        return;
-    }
-    for (int k = lane; k < Txw; k += 64) {
-        const int x = x0 + k;
-        if (x < W && bestL[k] != KEY_NONE) atomicMin(&A.keyL[orow + x], bestL[k]);
-    }
-    if (A.keyR) {
-        for (int k = lane; k < nRcw; k += 64) {
-            const int xr = xrc_lo + k;
-            if ((unsigned)xr < (unsigned)W && bestR[k] != KEY_NONE) atomicMin(&A.keyR[orow + xr], bestR[k]);
-        }
-    }
+#define ASW_EPI_RD ASW_RD
+#define ASW_EPI_LIVE active
+#define ASW_EPI_XG(live) xg
+#define ASW_EPI_DG(live) dg
+#define ASW_EPI_TX Txw
+#define ASW_EPI_NRC nRcw
+#define ASW_EPI_TID lane
+#define ASW_EPI_NTHR 64
+#define ASW_EPI_SYNC() asw_wave_sync()
+#define ASW_EPI_ROW orow
+#include "asw_epilogue.inc"
 }
 
 }  // namespace ssamd
