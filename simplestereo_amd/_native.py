@@ -9,8 +9,8 @@ import os
 
 from .build import LIB_PATH as _DEFAULT_LIB_PATH
 
-# experiments only (tools/build_variants.sh): another build of the same library is loaded only when the caller says
-# twice that this is an experiment -- ablation builds compute wrong maps by construction
+# experiments only (a library built from another source tree, tools/ab_tree.py): another build of the same library is loaded
+# only when the caller says twice that this is an experiment -- such a build need not compute the product's maps
 LIB_PATH = _DEFAULT_LIB_PATH
 if os.environ.get("SSAMD_LIB"):
     if os.environ.get("SSAMD_EXPERIMENT") != "1":

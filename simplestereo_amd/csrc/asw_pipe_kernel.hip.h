@@ -42,10 +42,6 @@
 #include "lab_kernels.hip.h"
 #endif
 
-#ifndef SSAMD_PIPE_SENTINEL       // 0: the round-2 weight build with masks (A/B builds of tools/build_variants.sh)
-#define SSAMD_PIPE_SENTINEL 1
-#endif
-
 namespace ssamd {
 
 #ifndef SSAMD_KERNEL_TU
@@ -273,7 +269,7 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(
             // a tap column outside the image gets L = +inf: colour distance +inf, exp2(-inf) = +0 -- the weight 0 the
             // reference's bounds test gives (_passive.cpp:60-62), exactly and without a mask in the weight build
             PixRec v;
-            v.L = SSAMD_PIPE_SENTINEL ? __builtin_inff() : 0.f;
+            v.L = __builtin_inff();
             v.a = v.b = 0.f;
             v.bgrx = 0u;
             if ((unsigned)col < (unsigned)W) v = (isL ? rowL : rowR)[col];
@@ -356,15 +352,12 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(
             const float4 *const seg = (isL ? labLc : labRc) + cc;
             const int stride = isL ? g.SL : SR;
             float *const wout = (isL ? wL : wR) + cc + (rb - jb) * stride;
-            const int col0 = (isL ? x0 : xrc_lo) + cc - p;
-            const uint32_t cmask = cen.w != 0.f ? 0xffffffffu : 0u;
             int j = jb_t;
             const float4 *sp = seg + j;
             const float *pp = prow + j;
             float *wp = wout + j * stride;
-            int col = col0 + j;
             const int stride4 = ASW_WB * stride;
-            for (; j + ASW_WB <= je_t; j += ASW_WB, sp += ASW_WB, pp += ASW_WB, wp += stride4, col += ASW_WB) {
+            for (; j + ASW_WB <= je_t; j += ASW_WB, sp += ASW_WB, pp += ASW_WB, wp += stride4) {
                 float4 tp[ASW_WB];
                 float pr[ASW_WB], wv[ASW_WB];
 #pragma unroll
@@ -380,14 +373,7 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(
 #pragma unroll
                 for (int u = 0; u < ASW_WB; ++u) wv[u] = asw_weight_finish(wv[u], A.kC, pr[u]);
 #pragma unroll
-                for (int u = 0; u < ASW_WB; ++u) {
-                    if constexpr (SSAMD_PIPE_SENTINEL) {
-                        wp[u * stride] = wv[u];
-                    } else {
-                        const uint32_t m = (unsigned)(col + u) < (unsigned)W ? cmask : 0u;
-                        wp[u * stride] = __uint_as_float(__float_as_uint(wv[u]) & m);
-                    }
-                }
+                for (int u = 0; u < ASW_WB; ++u) wp[u * stride] = wv[u];
             }
             if (j < je_t) {
                 float4 tp[ASW_WB];
@@ -411,12 +397,7 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(
 #pragma unroll
                 for (int u = 0; u < ASW_WB; ++u) {  // past the segment end the clamped tap is simply rewritten
                     const int jj = min(j + u, je_t - 1);
-                    if constexpr (SSAMD_PIPE_SENTINEL) {
-                        wout[jj * stride] = wv[u];
-                    } else {
-                        const uint32_t m = (unsigned)(col0 + jj) < (unsigned)W ? cmask : 0u;
-                        wout[jj * stride] = __uint_as_float(__float_as_uint(wv[u]) & m);
-                    }
+                    wout[jj * stride] = wv[u];
                 }
             }
         }
@@ -424,28 +405,15 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(
     auto chunk_end = [&](int c) { return c == NC - 1 ? win : (c + 1) * JC; };
     const int nE = nL * ((g.DG + 1) >> 1);             // tasks of one e tile
     // everything chunk c of window row i can hide: see the file header.  cb = weight buffer chunk c reads.
-    // (SSAMD_ABLATE_*: phase-ablation builds of tools/build_variants.sh, never defined in the product)
     auto build_next = [&](int i, int c, int cb) {
         const bool more_rows = i + 1 < i_hi;
-#ifdef SSAMD_PIPE_BUILD_PRIO          // experiment (tools/build_variants.sh): the latency-bound build chains at a raised issue priority
-        __builtin_amdgcn_s_setprio(SSAMD_PIPE_BUILD_PRIO);
-#endif
-#ifndef SSAMD_ABLATE_STAGE
         if (c == 0 && more_rows) stage_row(i + 1);
-#endif
         // issued after the staged pixels are in LDS (their global loads are waited for with vmcnt(0), which would
         // also wait for these); lands under the chunk's taps, complete at the next barrier
         if (c == 0 && more_rows && A.evol) load_e(i + 1);
-#ifndef SSAMD_ABLATE_WEIGHTS
         if (c + 1 < NC) build_weights(i, (c + 1) * JC, chunk_end(c + 1), (cb ^ 1) * g.JCmax);
         else if (more_rows) build_weights(i + 1, 0, chunk_end(0), (cb ^ 1) * g.JCmax);
-#endif
-#ifndef SSAMD_ABLATE_E
         if (c >= 1 && more_rows && !A.evol) build_e(i + 1, (int)((long long)nE * (c - 1) / (NC - 1)), (int)((long long)nE * c / (NC - 1)));
-#endif
-#ifdef SSAMD_PIPE_BUILD_PRIO
-        __builtin_amdgcn_s_setprio(0);
-#endif
     };
 
     // ---- prologue: first window row staged, its e tile and its first weight chunk built (not overlapped: 1 / win of the work)
@@ -468,9 +436,6 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(
     {
         const int tidm = threadIdx.x;
         int xg, dg;
-#ifdef SSAMD_PIPE_PLAIN_LANES          // round-2 order (A/B builds of tools/build_variants.sh): thread = xg * DGe + dg
-        xg = tidm / DGe; dg = tidm - xg * DGe;
-#else
         // Lane order (round 3).  The LDS serves a ds_read_b128 in groups of 16 lanes and a ds_read_b32 in groups of 32;
         // with thread = xg * DGe + dg and DGe no multiple of 16 (49 at 1080p / D 0..192) a third of the 16-lane groups
         // straddle two column groups, whose right-weight blocks and e dwords then collide (rocprofv3: 23 % of the LDS
@@ -490,7 +455,6 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(
             xg = Lo ? q / Lo : g.XG;                 // (q >= XG * Lo: beyond the active threads)
             dg = 16 * F + (Lo ? q - xg * Lo : 0);
         }
-#endif
         pk_xd = xg | (dg << 16);
         const bool tile_live = tidm < nact && x0 + RX * xg < W && dlo + ASW_RD * dg <= A.maxD &&
                                x0 + RX * xg + RX - 1 - (dlo + ASW_RD * dg) >= 0;
@@ -505,14 +469,11 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(
 
 #pragma nounroll                      // (NC is a compile-time 2 in the static instantiations: two copies of the tap loop cost VGPRs -> scratch)
         for (int c = 0; c < NC; ++c) {
-#ifndef SSAMD_ABLATE_BARRIER          // (ablation build: how much of the time is waiting at this barrier; results are wrong without it)
             __syncthreads();       // buffers of chunk (i, c) complete; every wave is done with chunk (i, c) - 1
-#endif
             const int jc = c * JC, jend = chunk_end(c);
             const int rb = cb * g.JCmax;
             // waves 0-3 (one per SIMD) build first, their two SIMD-mates aggregate first and build afterwards
             if (phase == 0) build_next(i, c, cb);
-#ifndef SSAMD_ABLATE_AGG
             if (run) {
                 // e-row and weight pointers are derived per chunk from the packed thread coordinates: nothing but those,
                 // the e window and the accumulators stays live across a build
@@ -568,7 +529,6 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(
                     if constexpr (STATIC) { erow += RX * SEC; wlp += RX * SLC; wrp += RX * SRC; }
                 }
             }
-#endif
             if (phase != 0) build_next(i, c, cb);
             cb ^= 1;
         }

@@ -12,7 +12,9 @@
 //   * e tile: one 8-byte slot per disparity group and tap column (bytes 0..5 = the six truncated differences, written by
 //     asw_tad_volume_kernel in its rd = 6 mode), read with one ds_read_b64;
 //   * right weights: nine consecutive floats from an 8-byte-aligned address (the groups are six apart), five ds_read_b64;
-//   * the build is always the merged one (one list of left and right centres, asw_wave_kernel.hip.h).
+//   * the build is always the merged one (one list of left and right centres).
+// Everything up to and including that build, and the staging of an image row, is the wave kernel's text (asw_wave_front.inc,
+// asw_wave_row.inc); what is written here is the e window and the tap step.
 // Shares AswWaveArgs / AswWaveGeom (RD = 6, Se = bytes per e column) and the host path of the wave kernel.
 #pragma once
 #include "asw_wave_kernel.hip.h"
@@ -35,7 +37,7 @@ __device__ __forceinline__ void asw_row_unpack6(AswRow6 &row, const uint2 packed
 }
 
 // KM: build rounds known at compile time (3 for the class default), 0: counted at run time
-// CREG: window centres in registers (see asw_aggregate_wave_kernel): no cen array in LDS, two instead of three reads per weight pair.
+// CREG: window centres in registers (asw_wave_front.inc): no cen array in LDS, two instead of three reads per weight pair.
 // (Round 4 also built a 128-VGPR form -- four waves per SIMD, build rounds one after the other -- and an e tile without its spare
 //  slot, Se = 24: the 96 registers of accumulators and e window leave too little, 6.49 vs 6.07 ms at 1080p / D 0..16 and 4.15 vs
 //  3.45 ms with register centres; Se = 24 bought a resident wave at win >= 31 and cost 10-16 % below.  profiles/r04_wave6_*.txt.)
@@ -43,162 +45,21 @@ template <bool WITH_COSTS, int KM, bool CREG = false>
 __global__ __launch_bounds__(256, 3) void asw_aggregate_wave6_kernel(const AswWaveArgs A)
 {
     static_assert(!CREG || KM > 0, "register centres need the straight-line build");
+    // build_merged keeps all reads of a straight-line build in flight for RX == 4 && KM <= 3 and goes round by round above that;
+    // every instance (asw_instances.inc: KM 0, 2, 3) is built the first way, and a fourth round has to be measured before it ships
+    static_assert(KM <= 3, "asw_wave_front.inc: KM > 3 selects the serial build, which this kernel has never been measured with");
     constexpr int RX = 4, RD = 6, NWR = 10;          // nine right weights used, read as five pairs
-    extern __shared__ __attribute__((aligned(16))) char smem_all[];
-    const AswWaveGeom &g = A.g;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    char *const smem = smem_all + wave * g.wave_lds;
-    float *const wS = reinterpret_cast<float *>(smem + g.off_w);
-    float4 *const cenLab = reinterpret_cast<float4 *>(smem + g.off_cen);
-    float4 *const pixL = reinterpret_cast<float4 *>(smem + g.off_pixL);
-    float4 *const pixR = reinterpret_cast<float4 *>(smem + g.off_pixR);
-    unsigned char *const eT = reinterpret_cast<unsigned char *>(smem + g.off_e);
-    u64 *const bestL = reinterpret_cast<u64 *>(smem + g.off_bestL);
-    u64 *const bestR = reinterpret_cast<u64 *>(smem + g.off_bestR);
-
-    const int W = A.W, win = A.win, p = A.pad;
-    const int Txw = g.Txw, Dc = g.Dc, nLw = g.nLw, nRcw = g.nRcw, nRw = g.nRw, Se = g.Se;
-    const int x0 = (blockIdx.x * g.waves + wave) * Txw;
-    if (x0 >= W) return;
-    const int y = asw_out_row(A, blockIdx.y);
-    const int dlo = A.minD, dhi = dlo + Dc - 1;
-    const size_t orow = (size_t)(y - A.row0) * W;
-    if (min(x0 + Txw - 1, W - 1) - dlo < 0) {                   // no candidate the reference evaluates in this strip
-        if (A.disp)
-            for (int k = lane; k < Txw && x0 + k < W; k += 64) A.disp[orow + x0 + k] = (int16_t)(x0 + k);
-        return;
-    }
-    const int segL_lo = x0 - p, xrc_lo = x0 - dhi, segR_lo = xrc_lo - p;
-    const int ncen = Txw + nRcw;
-    const int xg = lane / g.DG, dg = lane - xg * g.DG;
-    const bool active = lane < g.lanes;
-
-    float accN[RX][RD], accS[RX][RD];
-#pragma unroll
-    for (int a = 0; a < RX; ++a)
-#pragma unroll
-        for (int b = 0; b < RD; ++b) { accN[a][b] = 0.f; accS[a][b] = 0.f; }
-    float cenx[CREG ? KM : 1], ceny[CREG ? KM : 1], cenz[CREG ? KM : 1];      // CREG: Lab of the centres lane, lane + 64, ... (row y)
-    if constexpr (CREG) {
-#pragma unroll
-        for (int r = 0; r < KM; ++r) {
-            const int c = 64 * r + lane;
-            const bool isL = c < Txw;
-            const int ccol = isL ? x0 + c : xrc_lo + (c - Txw);
-            cenx[r] = ceny[r] = cenz[r] = 0.f;
-            if (c < ncen && (unsigned)ccol < (unsigned)W) {
-                const PixRec q = (isL ? A.recL : A.recR)[(size_t)y * W + ccol];
-                cenx[r] = q.L; ceny[r] = q.a; cenz[r] = q.b;
-            }
-        }
-    } else {
-        for (int c = lane; c < ncen; c += 64) {                  // window centres (row y)
-            const bool isL = c < Txw;
-            const int ccol = isL ? x0 + c : xrc_lo + (c - Txw);
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if ((unsigned)ccol < (unsigned)W) {
-                const PixRec q = (isL ? A.recL : A.recR)[(size_t)y * W + ccol];
-                v = make_float4(q.L, q.a, q.b, 1.f);
-            }
-            cenLab[c] = v;
-        }
-    }
-    // merged support-weight build of two tap columns (j, j + 1): see asw_aggregate_wave_kernel
-    typedef float v4f __attribute__((ext_vector_type(4)));
-    typedef __attribute__((address_space(3))) const v4f *lds_v4;
-    typedef __attribute__((address_space(3))) float *lds_f1;
-    auto ld4 = [](uint32_t a) { const v4f v = *(lds_v4)a; return make_float4(v.x, v.y, v.z, v.w); };
-    const uint32_t sbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char *)smem;
-    const uint32_t lane16 = lane * 16, lane4 = lane * 4;
-    auto weight = [&](const float4 &ce, const float4 &tp, float pj) {
-        const float dL = tp.x - ce.x, da = tp.y - ce.y, db = tp.z - ce.z;
-        const float dist = __builtin_amdgcn_sqrtf(fmaf(db, db, fmaf(da, da, dL * dL)));
-        return asw_weight_finish(dist, A.kC, pj);
-    };
-    const int wrow = g.SLw + g.SRw;
-    uint32_t tapoff[KM > 0 ? KM : 1];
-#pragma unroll
-    for (int r = 0; r < (KM > 0 ? KM : 1); ++r) {
-        const int c = 64 * r + lane;
-        tapoff[r] = 16u * (uint32_t)c + (c < Txw ? 0u : 32u * (uint32_t)p);
-    }
-    auto build = [&](int j, float pj0, float pj1) {
-        uint32_t tap_b = sbase + g.off_pixL + 16 * j, cen_b = sbase + g.off_cen, dst_b = sbase + g.off_w;
-        asm volatile("" : "+s"(tap_b), "+s"(cen_b), "+s"(dst_b));
-        const uint32_t row1 = (uint32_t)wrow * 4;
-        if constexpr (CREG) {
-            const uint32_t da = dst_b + lane4, db_ = da + row1;
-            float4 ta_[KM], tb[KM];
-#pragma unroll
-            for (int r = 0; r < KM; ++r) {
-                const uint32_t ta = tap_b + tapoff[r];
-                ta_[r] = ld4(ta); tb[r] = ld4(ta + 16);
-            }
-#pragma unroll
-            for (int r = 0; r < KM; ++r) asm volatile("" ::"v"(ta_[r].w), "v"(tb[r].w) : "memory");
-#pragma unroll
-            for (int r = 0; r < KM; ++r) {
-                const float4 ce = make_float4(cenx[r], ceny[r], cenz[r], 0.f);
-                *(lds_f1)(da + 256 * r) = weight(ce, ta_[r], pj0);
-                *(lds_f1)(db_ + 256 * r) = weight(ce, tb[r], pj1);
-            }
-            return;
-        }
-        if constexpr (KM > 0) {
-            const uint32_t ca = cen_b + lane16, da = dst_b + lane4, db_ = da + row1;
-            float4 ce[KM], ta_[KM], tb[KM];
-#pragma unroll
-            for (int r = 0; r < KM; ++r) {
-                const uint32_t ta = tap_b + tapoff[r];
-                ce[r] = ld4(ca + 1024 * r); ta_[r] = ld4(ta); tb[r] = ld4(ta + 16);
-            }
-#pragma unroll
-            for (int r = 0; r < KM; ++r) asm volatile("" ::"v"(ce[r].w), "v"(ta_[r].w), "v"(tb[r].w) : "memory");
-#pragma unroll
-            for (int r = 0; r < KM; ++r) {
-                *(lds_f1)(da + 256 * r) = weight(ce[r], ta_[r], pj0);
-                *(lds_f1)(db_ + 256 * r) = weight(ce[r], tb[r], pj1);
-            }
-            return;
-        }
-        for (int k = 0; k < ncen; k += 64) {              // rounds counted at run time
-            const int c = k + lane;
-            const uint32_t ca = cen_b + lane16 + k * 16, ta = tap_b + lane16 + k * 16 + (c < Txw ? 0u : 32u * (uint32_t)p),
-                           da = dst_b + lane4 + k * 4;
-            const float4 ce0 = ld4(ca), ta0 = ld4(ta), tb0 = ld4(ta + 16);
-            asm volatile("" ::"v"(ce0.w), "v"(ta0.w), "v"(tb0.w) : "memory");
-            *(lds_f1)da = weight(ce0, ta0, pj0);
-            *(lds_f1)(da + row1) = weight(ce0, tb0, pj1);
-        }
-    };
+    // ---- LDS slice, strip, accumulators, window centres, the merged support-weight build: shared with asw_aggregate_wave_kernel
+#include "asw_wave_front.inc"
+    auto build = [&](int j, float pj0, float pj1) { build_merged(sbase + g.off_pixL + 16 * j, sbase + g.off_cen, sbase + g.off_w, pj0, pj1); };
 
     const int i_lo = max(0, p - y), i_hi = min(win, A.H + p - y);
     int proxv = 0;
     for (int i = i_lo; i < i_hi; ++i) {
         const int r = y - p + i;
         asw_wave_sync();                 // the previous window row's taps are done with the pixel and e rows
-        {
-            const unsigned char *const src = A.evol + (((size_t)(r - A.erow0)) * (size_t)A.evolW + x0) * Se;
-            const int bytes = nLw * Se;
-            for (int k = 0; k < bytes; k += 1024)
-                if (k + lane * 16 < bytes)
-                    __builtin_amdgcn_global_load_lds((const void *)(src + k + lane * 16),
-                                                     (__attribute__((address_space(3))) void *)(eT + k), 16, 0, 0);
-            proxv = __builtin_bit_cast(int, A.prox[i * win + min(lane, win - 1)]);   // lane j: proximity weight of tap column j
-            const PixRec *const rowL = A.recL + (size_t)r * W, *const rowR = A.recR + (size_t)r * W;
-            for (int k = lane; k < nLw + nRw; k += 64) {
-                const bool isL = k < nLw;
-                const int idx = isL ? k : k - nLw;
-                const int col = (isL ? segL_lo : segR_lo) + idx;
-                float4 v = make_float4(__builtin_inff(), 0.f, 0.f, 0.f);      // outside the image: weight +0 (see the wave kernel)
-                if ((unsigned)col < (unsigned)W) {
-                    const PixRec q = (isL ? rowL : rowR)[col];
-                    v = make_float4(q.L, q.a, q.b, 0.f);
-                }
-                (isL ? pixL : pixR)[idx] = v;
-            }
-        }
+        // ---- this image row: e tile by LDS-DMA (one contiguous block of the volume), proxv, Lab of the tap columns
+#include "asw_wave_row.inc"
         asw_wave_sync();
         // e window: rows ul = RX xg + n of the tile, 8-byte slot dg
         // (lanes past the last column group -- lane 63 of the 21 x 3 class-default strip -- read the last group's e rows: the tile has no slack behind it)

@@ -60,8 +60,6 @@ __device__ __forceinline__ void asw_wave_sync()
     __builtin_amdgcn_wave_barrier();
 }
 
-typedef float asw_v2f __attribute__((ext_vector_type(2)));
-
 // LDS instructions of one wave execute in issue order, so a wave's ds_read sees its own earlier ds_write without
 // waiting for it; only the compiler must keep the order.
 __device__ __forceinline__ void asw_wave_order()
@@ -70,122 +68,25 @@ __device__ __forceinline__ void asw_wave_order()
     __builtin_amdgcn_wave_barrier();
 }
 
-#ifndef SSAMD_WAVE4_OCC          // experiment builds (tools/build_variants.sh): waves per SIMD of the 4-column tile,
-#define SSAMD_WAVE4_OCC 4        // and whether its build keeps two rounds' reads in flight
-#endif
-#ifndef SSAMD_WAVE4_PAIR
-#define SSAMD_WAVE4_PAIR 1
-#endif
-#ifndef SSAMD_WAVE8_OCC
-#define SSAMD_WAVE8_OCC 3
-#endif
-#ifndef SSAMD_WAVE_PKMUL         // 1: the tap products as v_pk_mul_f32 pairs (measured: 1.5-4 % slower)
-#define SSAMD_WAVE_PKMUL 0
-#endif
 // KL, KR: build rounds (64 centres each) of the left and of the right part when the host knows them at compile time
 // (the build is then straight-line code with immediate offsets); 0: counted at run time.
-// KM (round 3): rounds of the MERGED build -- the strip's Txw left and nRcw right centres as one list of Txw + nRcw
-// entries dealt to the lanes 64 at a time, instead of ceil(Txw / 64) + ceil(nRcw / 64) rounds with two part-filled
-// last rounds (class default D 0..16, 4-column tile: 48 + 67 centres = 2 rounds instead of 1 + 2).  The two parts
-// read different pixel rows; pixR follows pixL in LDS, so the tap address of list entry c is
-// pixL + 16 (c + j) + (c < Txw ? 0 : 32 pad): one per-lane constant per round (tapoff), set up once per wave.
-// CREG (round 4, with KM > 0): the centres a lane evaluates are the SAME in every build of the kernel (list entries lane,
-// lane + 64, ...), so their Lab values are loaded once from the records into 3 KM registers instead of being kept in an LDS
-// array and re-read twice per tap-column pair: a third fewer LDS reads per weight, and the wave's LDS slice loses 16 bytes
-// per centre -- at D 0..7 / win 35 (124-column strips, 255 centres) that is 13.9 -> 9.9 KB, 11 -> 16 resident waves per CU.
+// KM (round 3): rounds of the MERGED build, CREG (round 4, with KM > 0): the window centres in registers -- both are
+// explained with the build they select, in asw_wave_front.inc.
 template <bool WITH_COSTS, int RX, int KL = 0, int KR = 0, int KM = 0, bool CREG = false>
-__global__ __launch_bounds__(256, RX == 8 ? SSAMD_WAVE8_OCC : SSAMD_WAVE4_OCC) void asw_aggregate_wave_kernel(const AswWaveArgs A)
+__global__ __launch_bounds__(256, RX == 8 ? 3 : 4) void asw_aggregate_wave_kernel(const AswWaveArgs A)
 {
     static_assert(!CREG || KM > 0, "register centres need the straight-line merged build");
-    constexpr int NWR = asw_nwr(RX);
-    extern __shared__ __attribute__((aligned(16))) char smem_all[];
-    const AswWaveGeom &g = A.g;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    char *const smem = smem_all + wave * g.wave_lds;
-    float *const wS = reinterpret_cast<float *>(smem + g.off_w);            // [SLw + SRw]: left weights, then right weights
-    float4 *const cenLab = reinterpret_cast<float4 *>(smem + g.off_cen);    // [Txw + nRcw]
-    float4 *const pixL = reinterpret_cast<float4 *>(smem + g.off_pixL);     // [nLw] Lab of the current image row
-    float4 *const pixR = reinterpret_cast<float4 *>(smem + g.off_pixR);     // [nRw]
-    unsigned char *const eT = reinterpret_cast<unsigned char *>(smem + g.off_e);   // [nLw][Se]
-    u64 *const bestL = reinterpret_cast<u64 *>(smem + g.off_bestL);
-    u64 *const bestR = reinterpret_cast<u64 *>(smem + g.off_bestR);
-
-    const int W = A.W, win = A.win, p = A.pad;
-    const int Txw = g.Txw, Dc = g.Dc, nLw = g.nLw, nRcw = g.nRcw, nRw = g.nRw, Se = g.Se;
-    const int x0 = (blockIdx.x * g.waves + wave) * Txw;
-    if (x0 >= W) return;                                         // (no workgroup barrier anywhere: waves are independent)
-    const int y = asw_out_row(A, blockIdx.y);
-    const int dlo = A.minD, dhi = dlo + Dc - 1;
-    const size_t orow = (size_t)(y - A.row0) * W;
-    if (min(x0 + Txw - 1, W - 1) - dlo < 0) {                   // no candidate the reference evaluates in this strip
-        if (A.disp)
-            for (int k = lane; k < Txw && x0 + k < W; k += 64) A.disp[orow + x0 + k] = (int16_t)(x0 + k);
-        return;
-    }
-    const int segL_lo = x0 - p, xrc_lo = x0 - dhi, segR_lo = xrc_lo - p;
-    const int ncen = Txw + nRcw;
-    const int xg = lane / g.DG, dg = lane - xg * g.DG;
-    const bool active = lane < g.lanes;
-
-    float accN[RX][ASW_RD], accS[RX][ASW_RD];
-#pragma unroll
-    for (int a = 0; a < RX; ++a)
-#pragma unroll
-        for (int b = 0; b < ASW_RD; ++b) { accN[a][b] = 0.f; accS[a][b] = 0.f; }
-    float cenx[CREG ? KM : 1], ceny[CREG ? KM : 1], cenz[CREG ? KM : 1];      // CREG: Lab of the centres lane, lane + 64, ... (row y)
-    if constexpr (CREG) {
-#pragma unroll
-        for (int r = 0; r < KM; ++r) {
-            const int c = 64 * r + lane;
-            const bool isL = c < Txw;
-            const int ccol = isL ? x0 + c : xrc_lo + (c - Txw);
-            cenx[r] = ceny[r] = cenz[r] = 0.f;
-            if (c < ncen && (unsigned)ccol < (unsigned)W) {
-                const PixRec q = (isL ? A.recL : A.recR)[(size_t)y * W + ccol];
-                cenx[r] = q.L; ceny[r] = q.a; cenz[r] = q.b;
-            }
-        }
-    } else {
-        for (int c = lane; c < ncen; c += 64) {                  // window centres (row y)
-            const bool isL = c < Txw;
-            const int ccol = isL ? x0 + c : xrc_lo + (c - Txw);
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if ((unsigned)ccol < (unsigned)W) {
-                const PixRec q = (isL ? A.recL : A.recR)[(size_t)y * W + ccol];
-                v = make_float4(q.L, q.a, q.b, 1.f);
-            }
-            cenLab[c] = v;
-        }
-    }
-    // Support weights of one tap column: lane l evaluates the centres l, l + 64, ... of the left and of the right part.
-    // A tap column outside the image has L = +inf and so a zero weight; centres outside the image only feed candidates
-    // the winner-take-all never looks at.
-    // Addresses are LDS byte offsets = a wave-uniform base (SGPR) + the lane's 16 * lane or 4 * lane: the only vector
-    // registers the build keeps between steps are those two (pointers per array would not fit next to the accumulators).
-    typedef float v4f __attribute__((ext_vector_type(4)));
-    typedef __attribute__((address_space(3))) const v4f *lds_v4;
-    typedef __attribute__((address_space(3))) float *lds_f1;
-    auto ld4 = [](uint32_t a) { const v4f v = *(lds_v4)a; return make_float4(v.x, v.y, v.z, v.w); };
-    const uint32_t sbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char *)smem;
-    const uint32_t lane16 = lane * 16, lane4 = lane * 4;
-    // (no lane guards: reads up to 127 entries past a part's end stay inside the wave's LDS slice and the weight rows
-    // are padded to whole rounds, so the surplus lanes of the last round write weights nobody reads)
-    auto weight = [&](const float4 &ce, const float4 &tp, float pj) {
-        const float dL = tp.x - ce.x, da = tp.y - ce.y, db = tp.z - ce.z;
-        const float dist = __builtin_amdgcn_sqrtf(fmaf(db, db, fmaf(da, da, dL * dL)));
-        return asw_weight_finish(dist, A.kC, pj);
-    };
-    // Two tap columns (j, j + 1) per build: a centre is read once for both, and the wave pays the LDS round trip of a
-    // build once per two aggregation steps.  Weight row q = column parity, at wS + q * wrow.
-    const int wrow = g.SLw + g.SRw;
+    constexpr int NWR = asw_nwr(RX), RD = ASW_RD;
+    // ---- LDS slice, strip, accumulators, window centres, the merged support-weight build: shared with asw_aggregate_wave6_kernel
+#include "asw_wave_front.inc"
+    // the separate-rounds build (KL / KR, or counted): the left and the right part of the centre list one after the other
     auto build_part = [&](auto rounds, uint32_t tap_b, uint32_t cen_b, uint32_t dst_b, int n, float pj0, float pj1) {
         asm volatile("" : "+s"(tap_b), "+s"(cen_b), "+s"(dst_b));        // opaque: base + lane sums are formed here, per build
         const uint32_t row1 = (uint32_t)wrow * 4;
         constexpr int K = decltype(rounds)::value;
         if constexpr (K > 0) {                           // round count known: one address per array, immediate offsets
             const uint32_t ca = cen_b + lane16, ta = tap_b + lane16, da = dst_b + lane4, db_ = da + row1;
-            if constexpr ((RX == 4 || SSAMD_WAVE8_OCC == 2) && K <= 3) {           // registers to spare: all reads of the part in flight together
+            if constexpr (RX == 4 && K <= 3) {           // registers to spare: all reads of the part in flight together
                 float4 ce[K], ta_[K], tb[K];
 #pragma unroll
                 for (int r = 0; r < K; ++r) { ce[r] = ld4(ca + 1024 * r); ta_[r] = ld4(ta + 1024 * r); tb[r] = ld4(ta + 1024 * r + 16); }
@@ -209,7 +110,7 @@ __global__ __launch_bounds__(256, RX == 8 ? SSAMD_WAVE8_OCC : SSAMD_WAVE4_OCC) v
         }
         int k = 0;
         // 4-column tile: two rounds per trip, all six reads in flight together (the 8-column tile has no registers for that)
-        if constexpr (RX == 4 && SSAMD_WAVE4_PAIR) for (; k + 64 < n; k += 128) {
+        if constexpr (RX == 4) for (; k + 64 < n; k += 128) {
             const uint32_t ca = cen_b + lane16 + k * 16, ta = tap_b + lane16 + k * 16, da = dst_b + lane4 + k * 4;
             const float4 ce0 = ld4(ca), ta0 = ld4(ta), tb0 = ld4(ta + 16);
             const float4 ce1 = ld4(ca + 1024), ta1 = ld4(ta + 1024), tb1 = ld4(ta + 1040);
@@ -221,72 +122,6 @@ __global__ __launch_bounds__(256, RX == 8 ? SSAMD_WAVE8_OCC : SSAMD_WAVE4_OCC) v
         }
         for (; k < n; k += 64) {                         // single rounds
             const uint32_t ca = cen_b + lane16 + k * 16, ta = tap_b + lane16 + k * 16, da = dst_b + lane4 + k * 4;
-            const float4 ce0 = ld4(ca), ta0 = ld4(ta), tb0 = ld4(ta + 16);
-            asm volatile("" ::"v"(ce0.w), "v"(ta0.w), "v"(tb0.w) : "memory");
-            *(lds_f1)da = weight(ce0, ta0, pj0);
-            *(lds_f1)(da + row1) = weight(ce0, tb0, pj1);
-        }
-    };
-    // merged build: per-lane tap offsets of the compile-time rounds (see the template comment)
-    uint32_t tapoff[KM > 0 ? KM : 1];
-#pragma unroll
-    for (int r = 0; r < (KM > 0 ? KM : 1); ++r) {
-        const int c = 64 * r + lane;
-        tapoff[r] = 16u * (uint32_t)c + (c < Txw ? 0u : 32u * (uint32_t)p);
-    }
-    auto build_merged = [&](uint32_t tap_b, uint32_t cen_b, uint32_t dst_b, float pj0, float pj1) {
-        asm volatile("" : "+s"(tap_b), "+s"(cen_b), "+s"(dst_b));
-        const uint32_t row1 = (uint32_t)wrow * 4;
-        if constexpr (CREG) {                            // centres in registers: two tap reads per weight pair, all in flight together
-            const uint32_t da = dst_b + lane4, db_ = da + row1;
-            float4 ta_[KM], tb[KM];
-#pragma unroll
-            for (int r = 0; r < KM; ++r) {
-                const uint32_t ta = tap_b + tapoff[r];
-                ta_[r] = ld4(ta); tb[r] = ld4(ta + 16);
-            }
-#pragma unroll
-            for (int r = 0; r < KM; ++r) asm volatile("" ::"v"(ta_[r].w), "v"(tb[r].w) : "memory");
-#pragma unroll
-            for (int r = 0; r < KM; ++r) {
-                const float4 ce = make_float4(cenx[r], ceny[r], cenz[r], 0.f);
-                *(lds_f1)(da + 256 * r) = weight(ce, ta_[r], pj0);
-                *(lds_f1)(db_ + 256 * r) = weight(ce, tb[r], pj1);
-            }
-            return;
-        }
-        if constexpr (KM > 0) {
-            const uint32_t ca = cen_b + lane16, da = dst_b + lane4, db_ = da + row1;
-            if constexpr (RX == 4 && KM <= 3) {          // registers to spare: all reads of the build in flight together
-                float4 ce[KM], ta_[KM], tb[KM];
-#pragma unroll
-                for (int r = 0; r < KM; ++r) {
-                    const uint32_t ta = tap_b + tapoff[r];
-                    ce[r] = ld4(ca + 1024 * r); ta_[r] = ld4(ta); tb[r] = ld4(ta + 16);
-                }
-#pragma unroll
-                for (int r = 0; r < KM; ++r) asm volatile("" ::"v"(ce[r].w), "v"(ta_[r].w), "v"(tb[r].w) : "memory");
-#pragma unroll
-                for (int r = 0; r < KM; ++r) {
-                    *(lds_f1)(da + 256 * r) = weight(ce[r], ta_[r], pj0);
-                    *(lds_f1)(db_ + 256 * r) = weight(ce[r], tb[r], pj1);
-                }
-                return;
-            }
-#pragma unroll
-            for (int r = 0; r < KM; ++r) {
-                const uint32_t ta = tap_b + tapoff[r];
-                const float4 ce0 = ld4(ca + 1024 * r), ta0 = ld4(ta), tb0 = ld4(ta + 16);
-                asm volatile("" ::"v"(ce0.w), "v"(ta0.w), "v"(tb0.w));   // keeps the reads ds_read_b128
-                *(lds_f1)(da + 256 * r) = weight(ce0, ta0, pj0);
-                *(lds_f1)(db_ + 256 * r) = weight(ce0, tb0, pj1);
-            }
-            return;
-        }
-        for (int k = 0; k < ncen; k += 64) {              // rounds counted at run time
-            const int c = k + lane;
-            const uint32_t ca = cen_b + lane16 + k * 16, ta = tap_b + lane16 + k * 16 + (c < Txw ? 0u : 32u * (uint32_t)p),
-                           da = dst_b + lane4 + k * 4;
             const float4 ce0 = ld4(ca), ta0 = ld4(ta), tb0 = ld4(ta + 16);
             asm volatile("" ::"v"(ce0.w), "v"(ta0.w), "v"(tb0.w) : "memory");
             *(lds_f1)da = weight(ce0, ta0, pj0);
@@ -308,33 +143,8 @@ __global__ __launch_bounds__(256, RX == 8 ? SSAMD_WAVE8_OCC : SSAMD_WAVE4_OCC) v
     for (int i = i_lo; i < i_hi; ++i) {
         const int r = y - p + i;
         asw_wave_sync();                 // the previous window row's taps are done with the pixel and e rows
-        // ---- this image row: e tile by LDS-DMA (one contiguous block of the volume), Lab of the tap columns
-#ifdef SSAMD_WABLATE_STAGE
-        if (i == i_lo)
-#endif
-        {
-            const unsigned char *const src = A.evol + (((size_t)(r - A.erow0)) * (size_t)A.evolW + x0) * Se;
-            const int bytes = nLw * Se;
-            for (int k = 0; k < bytes; k += 1024)
-                if (k + lane * 16 < bytes)
-                    __builtin_amdgcn_global_load_lds((const void *)(src + k + lane * 16),
-                                                     (__attribute__((address_space(3))) void *)(eT + k), 16, 0, 0);
-            proxv = __builtin_bit_cast(int, A.prox[i * win + min(lane, win - 1)]);   // lane j: proximity weight of tap column j
-            const PixRec *const rowL = A.recL + (size_t)r * W, *const rowR = A.recR + (size_t)r * W;
-            for (int k = lane; k < nLw + nRw; k += 64) {
-                const bool isL = k < nLw;
-                const int idx = isL ? k : k - nLw;
-                const int col = (isL ? segL_lo : segR_lo) + idx;
-                // a tap column outside the image gets L = +inf: its colour distance is +inf, exp2(-inf) = +0 and the
-                // weight is exactly the +0 the other kernels produce with a mask, without an instruction for it
-                float4 v = make_float4(__builtin_inff(), 0.f, 0.f, 0.f);
-                if ((unsigned)col < (unsigned)W) {
-                    const PixRec q = (isL ? rowL : rowR)[col];
-                    v = make_float4(q.L, q.a, q.b, 0.f);
-                }
-                (isL ? pixL : pixR)[idx] = v;
-            }
-        }
+        // ---- this image row: e tile by LDS-DMA (one contiguous block of the volume), proxv, Lab of the tap columns
+#include "asw_wave_row.inc"
         asw_wave_sync();
         // e window: rows ul = RX xg + n of the tile, dword dg
         const unsigned char *erow = eT + (RX * xg) * Se + 4 * dg;
@@ -347,28 +157,20 @@ __global__ __launch_bounds__(256, RX == 8 ? SSAMD_WAVE8_OCC : SSAMD_WAVE4_OCC) v
         const float *const wlp = wS + RX * xg;
         const float *const wrp = wS + g.SLw + (RX * xg - ASW_RD * dg + Dc - ASW_RD);
 
-        // (SSAMD_WABLATE_*: phase-ablation builds of tools/build_variants.sh, never defined in the product)
-#ifdef SSAMD_WABLATE_TAPS
-#define SSAMD_WAVE_TAPS_IF if (i == i_lo && j0 == 0)
-#else
-#define SSAMD_WAVE_TAPS_IF
-#endif
-#ifdef SSAMD_WABLATE_BUILD
-#define SSAMD_WAVE_BUILD(J) if (i == i_lo && (J) == 0) build(J, __builtin_bit_cast(float, __builtin_amdgcn_readlane(proxv, J)), \
-                                                              __builtin_bit_cast(float, __builtin_amdgcn_readlane(proxv, (J) + 1)));
-#else
-#define SSAMD_WAVE_BUILD(J) build(J, __builtin_bit_cast(float, __builtin_amdgcn_readlane(proxv, J)), \
-                                  __builtin_bit_cast(float, __builtin_amdgcn_readlane(proxv, (J) + 1)));
-#endif
         for (int j0 = 0; j0 < win; j0 += RX) {
 #define SSAMD_WSTEP(JJ)                                                                             \
     if (j0 + (JJ) < win) {                                                                          \
         const int j = j0 + (JJ);                                                                    \
         /* 1. even j: the support weights of tap columns j, j + 1 for the strip's centres (_passive.cpp:47-50, 71-74) */ \
-        if (((JJ) & 1) == 0) { asw_wave_order(); SSAMD_WAVE_BUILD(j) asw_wave_order(); }           \
+        if (((JJ) & 1) == 0) {                                                                      \
+            asw_wave_order();                                                                       \
+            build(j, __builtin_bit_cast(float, __builtin_amdgcn_readlane(proxv, j)),                \
+                  __builtin_bit_cast(float, __builtin_amdgcn_readlane(proxv, j + 1)));              \
+            asw_wave_order();                                                                       \
+        }                                                                                           \
         const float *const wl_ = wlp + ((JJ) & 1) * wrow, *const wr_ = wrp + ((JJ) & 1) * wrow;     \
         /* 2. the taps of column j (lanes past the last column group read inside the slice and are ignored) */ \
-        SSAMD_WAVE_TAPS_IF {                                                                        \
+        {                                                                                           \
             const uint32_t epk = *reinterpret_cast<const uint32_t *>(erow);                         \
             erow += Se;                                                                             \
             float wl[RX], wr[NWR];                                                                  \
@@ -391,19 +193,12 @@ __global__ __launch_bounds__(256, RX == 8 ? SSAMD_WAVE8_OCC : SSAMD_WAVE4_OCC) v
                 }                                                                                   \
             }                                                                                       \
             _Pragma("unroll") for (int xi = 0; xi < RX; xi += 2) {                                  \
-                /* the products of two columns; (xi, di) and (xi + 1, di + 1) share the right weight: with SSAMD_WAVE_PKMUL */ \
-                /* one v_pk_mul_f32 with a broadcast operand each (same IEEE products, 5 instead of 8 instructions) */ \
+                /* the products of two columns; (xi, di) and (xi + 1, di + 1) share the right weight.  (As v_pk_mul_f32 pairs */ \
+                /* with a broadcast operand -- same IEEE products, 5 instead of 8 instructions -- measured 1.5-4 % slower.) */ \
                 float w_[2][ASW_RD];                                                                \
                 _Pragma("unroll") for (int di = 0; di + 1 < ASW_RD; ++di) {                         \
                     const float s_ = wr[xi - di + ASW_RD - 1];                                      \
-                    if constexpr (SSAMD_WAVE_PKMUL) {                                               \
-                        const asw_v2f a_ = {wl[xi], wl[xi + 1]};                                    \
-                        const asw_v2f b_ = {s_, s_};                                                \
-                        const asw_v2f p_ = a_ * b_;                                                 \
-                        w_[0][di] = p_.x; w_[1][di + 1] = p_.y;                                     \
-                    } else {                                                                        \
-                        w_[0][di] = wl[xi] * s_; w_[1][di + 1] = wl[xi + 1] * s_;                   \
-                    }                                                                               \
+                    w_[0][di] = wl[xi] * s_; w_[1][di + 1] = wl[xi + 1] * s_;                       \
                 }                                                                                   \
                 w_[0][ASW_RD - 1] = wl[xi] * wr[xi];                                                \
                 w_[1][0] = wl[xi + 1] * wr[xi + ASW_RD];                                            \
@@ -421,8 +216,6 @@ __global__ __launch_bounds__(256, RX == 8 ? SSAMD_WAVE8_OCC : SSAMD_WAVE4_OCC) v
             SSAMD_WSTEP(0) SSAMD_WSTEP(1) SSAMD_WSTEP(2) SSAMD_WSTEP(3)
             if constexpr (RX == 8) { SSAMD_WSTEP(4) SSAMD_WSTEP(5) SSAMD_WSTEP(6) SSAMD_WSTEP(7) }
 #undef SSAMD_WSTEP
-#undef SSAMD_WAVE_BUILD
-#undef SSAMD_WAVE_TAPS_IF
         }
     }
 

@@ -238,10 +238,6 @@ __global__ __launch_bounds__(GSW_MAX_THREADS, 4) void gsw_aggregate_kernel(const
         bool use[TY];                       // this thread group's rows
 #pragma unroll
         for (int t = 0; t < TY; ++t) use[t] = TY * grp + t < ny && (unsigned)(r - (yg + t) + p) < (unsigned)win;
-        // (SSAMD_GABLATE_*: phase-ablation builds of tools/build_variants.sh -- wrong maps by construction, never defined in the product)
-#ifdef SSAMD_GABLATE_W
-        if (r == r_lo)
-#endif
         {
             // a thread keeps one reference column c and walks (output row of the strip, tap column) with its centre pixel
             // fetched once per row.  (A flat deal of (row, tap column) pairs over the threads -- for tall strips of
@@ -286,9 +282,6 @@ __global__ __launch_bounds__(GSW_MAX_THREADS, 4) void gsw_aggregate_kernel(const
         //      the e writes of a wave fall into consecutive floats, the reference pixels are broadcast
         //      reads and the target pixels consecutive 16-byte reads.  (nL is padded to a multiple of 4;
         //      the padding columns hold outside-the-image pixels and are never read by the taps.)
-#ifdef SSAMD_GABLATE_E
-        if (r == r_lo)
-#endif
         {
             const int lanesD = min(Dc, nthr), q = nthr / lanesD;
             const int dd0 = tid % lanesD, mq = tid / lanesD;
@@ -327,9 +320,6 @@ __global__ __launch_bounds__(GSW_MAX_THREADS, 4) void gsw_aggregate_kernel(const
         __syncthreads();
         if (r < r_hi) stage_row(r + 1, (r + 1) & 1);       // prefetch: its global latency sits under the taps below
 
-#ifdef SSAMD_GABLATE_TAPS
-        if (r == r_lo)
-#endif
         if (active) {
             const float *const wG = wS + (TY * grp) * win * Tx;       // this group's weight rows
             if constexpr (TY == 1) {

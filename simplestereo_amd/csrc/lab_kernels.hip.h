@@ -16,27 +16,7 @@ __constant__ float c_lin100[256];
 // double, one rounding to float) and returns the SAME float as the libm the reference links for every argument the conversion can
 // produce -- checked exhaustively on the host (oracle/libm_check.c) -- so the records hold exactly the reference's Lab values
 // rounded to float, and the fp64 tie-break pass the reference's doubles.  (Rounds 2-4 computed a correctly rounded cube root by
-// Newton steps: 99.90 % of the floats were glibc's, whose powf is within 0.82 ulp but not correctly rounded.  -DSSAMD_LAB_NEWTON
-// keeps that form for A/B builds.)
-#ifdef SSAMD_LAB_NEWTON
-__device__ __forceinline__ float lab_pow_third(float tf)
-{
-    const double t = (double)tf;
-    const float l2 = __builtin_amdgcn_logf(tf);                          // v_log_f32: log2(t)
-    float zf = __builtin_amdgcn_exp2f(l2 * -0.33333334f);              // t^(-1/3), ~1e-6
-    zf = zf * fmaf(-tf, zf * zf * zf, 4.0f) * 0.33333334f;              // one step in fp32: ~1e-7
-    double z = (double)zf;
-    {
-        const double z3 = z * z * z;
-        z = z * fma(-t, z3, 4.0) * (1.0 / 3.0);                          // z <- z (4 - t z^3) / 3: ~1e-14
-    }
-    const double c = t * z * z;
-    const double dy = (double)(float)(1 / 3.0) - 1.0 / 3.0;
-    return (float)fma(c * dy, (double)(l2 * 0.6931471805599453f), c);
-}
-#else
-__device__ __forceinline__ float lab_pow_third(float tf) { return glibc_powf_pos(tf, (float)(1 / 3.0)); }
-#endif
+// Newton steps: 99.90 % of the floats were glibc's, whose powf is within 0.82 ulp but not correctly rounded.)
 
 // The conversion's three lookup tables (sRGB byte -> linear * 100; glibc powf's log2 and exp2 tables) staged in LDS by the
 // record-producing kernels: 1.5 KB, indexed per lane.
@@ -57,11 +37,7 @@ struct LabTables {
 __device__ __forceinline__ double lab_f(double t, const LabTables &T)
 {
 #pragma clang fp contract(off)
-#ifdef SSAMD_LAB_NEWTON
-    if (t > 0.008856) return (double)lab_pow_third((float)t);
-#else
     if (t > 0.008856) return (double)glibc_powf_pos_t((float)t, (float)(1 / 3.0), T.log2tab, T.exp2tab);
-#endif
     return (7.787 * t) + (16.0 / 116.0);
 }
 

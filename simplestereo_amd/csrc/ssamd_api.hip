@@ -24,7 +24,7 @@
 #include "asw_wave_kernel.hip.h"
 #include "asw_wave6_kernel.hip.h"
 #include "asw_alt_kernels.hip.h"
-#ifndef SSAMD_SINGLE_TU          // (-DSSAMD_SINGLE_TU: everything in this translation unit, as until round 4: tools/build_variants.sh)
+// the phase-shifted and the six-per-lane kernels are instantiated in translation units of their own (asw_pipe_tu.hip, asw_wave6_tu.hip)
 namespace ssamd {
 #define SSAMD_PIPE_INSTANCE(C, SL, SR, SE) extern template __global__ void asw_aggregate_pipe_kernel<C, SL, SR, SE>(const AswArgs);
 #define SSAMD_PIPE_INSTANCE_CG(C, SL, SR, SE) extern template __global__ void asw_aggregate_pipe_kernel<C, SL, SR, SE, true>(const AswArgs);
@@ -34,7 +34,6 @@ namespace ssamd {
 #undef SSAMD_PIPE_INSTANCE_CG
 #undef SSAMD_WAVE6_INSTANCE
 }  // namespace ssamd
-#endif
 #include "gsw_kernels.hip.h"
 #include "lab_kernels.hip.h"
 #include "asw_exact_kernels.hip.h"
@@ -459,11 +458,7 @@ int get_prox(Ctx &c, int win, double gammaP, hipStream_t s, const float **out)
         for (int i = 0; i < win; ++i)
             for (int j = 0; j < win; ++j) {
                 const double di = i - p, dj = j - p;
-#if SSAMD_W_FOLD
-                host[(size_t)i * win + j] = (float)(-std::sqrt(di * di + dj * dj) / gammaP * 1.4426950408889634);      // log2 of the weight
-#else
                 host[(size_t)i * win + j] = (float)glibc_exp(-std::sqrt(di * di + dj * dj) / gammaP);      // (restated exp: see get_prox64)
-#endif
             }
     });
 }

@@ -93,7 +93,7 @@ def test_lab_conversion_vs_oracle(ss, tsukuba):
     _native.check(_native.lib().ssamd_bgr2lab(cube.ctypes.data, 1, cube.shape[1], lab2.ctypes.data, -1))
     ref2 = oracle.bgr2lab(cube)
     assert np.abs(lab2 - ref2).max() <= 1e-4
-    # the cube root is evaluated in fp64 (lab_pow_third): nearly every value is the reference's double rounded to float
+    # the cube root is evaluated in fp64 (glibc_powf_pos_t): nearly every value is the reference's double rounded to float
     assert float(np.mean(lab2 == ref2.astype(np.float32))) >= 0.995
 
 
