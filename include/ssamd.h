@@ -13,6 +13,9 @@
  *                           called from StereoGSW.compute, passive.py:153-156
  *   ssamd_iir_unwrap   <->  _unwrapping.infiniteImpulseResponse   simplestereo/_unwrapping.cpp:50-156
  *                           called from unwrapping.infiniteImpulseResponse, unwrapping.py:10-41
+ *   ssamd_np_unwrap    <->  np.unwrap(phase, discont=np.pi, axis=...), the default unwrapping of every getCloud
+ *                           simplestereo/active.py:739-745, 1026-1032, 1404-1410 (numpy in the reference; ssamd_np_unwrap_xy
+ *                           is the two calls of those lines, ssamd_ftp_phase with unwrap = 2 chains them)
  *   ssamd_ftp_phase    <->  the demodulation of StereoFTP.getCloud   simplestereo/active.py:675-737
  *                           (pure numpy in the reference: fft, band mask, ifft, angle; NOT the StereoFTP classes)
  *   ssamd_*_device     same operators on buffers already resident in HBM (no
@@ -41,7 +44,7 @@
 extern "C" {
 #endif
 
-#define SSAMD_ABI_VERSION 7      /* 7: ssamd_ftp_phase / ssamd_ftp_phase_device / ssamd_ftp_band and profile slot SSAMD_K_FTP; 6: ssamd_iir_unwrap / ssamd_iir_unwrap_device and profile slot SSAMD_K_UNWRAP; 5:ssamd_asw_exact_device_rows2 / _rectified_device (round 6: near-ties selected inside the aggregation kernels); 4: ssamd_asw_exact* (round 5); 3: GSW autotuning; 2: ssamd_set_option (round 3) + the multi-device and verification entry points added in round 2 */
+#define SSAMD_ABI_VERSION 8      /* 8: ssamd_np_unwrap / _device / _xy / _xy_device / _plan, ssamd_ftp_phase* unwrap = 2 and profile slot SSAMD_K_NPUNWRAP; 7: ssamd_ftp_phase / ssamd_ftp_phase_device / ssamd_ftp_band and profile slot SSAMD_K_FTP; 6: ssamd_iir_unwrap / ssamd_iir_unwrap_device and profile slot SSAMD_K_UNWRAP; 5:ssamd_asw_exact_device_rows2 / _rectified_device (round 6: near-ties selected inside the aggregation kernels); 4: ssamd_asw_exact* (round 5); 3: GSW autotuning; 2: ssamd_set_option (round 3) + the multi-device and verification entry points added in round 2 */
 
 #define SSAMD_OK 0
 #define SSAMD_EINVAL (-1)     /* bad argument (message tells which)            */
@@ -248,6 +251,33 @@ int ssamd_reproject_device(const int16_t *d_disparity, int h, int w, const doubl
 int ssamd_iir_unwrap(const double *phase, int n, int h, int w, double tau, double *out, int device);
 int ssamd_iir_unwrap_device(const double *d_phase, int n, int h, int w, double tau, double *d_out, void *stream);
 
+/* ---- numpy's unwrap: the reference's default unwrapping (active.py:739-745: np.unwrap along axis 1, then along axis 0) ------ */
+/* np.unwrap(p, discont, axis, period=period) on fp64 data, bit for bit (NaN where numpy has NaN).  Any C-contiguous array and
+ * axis are one geometry [outer][len][inner]: outer = product of the extents before the axis, len = the axis, inner = product of
+ * the extents after it; every line of len samples at stride inner is scanned on its own:
+ *     dd = p[i] - p[i-1];  ddmod = mod(dd + period/2, period) - period/2, set to +period/2 where it is -period/2 and dd > 0;
+ *     c = ddmod - dd, 0 where |dd| < discont;  out[0] = p[0], out[i] = p[i] + (c[1] + ... + c[i] summed left to right)
+ * in fp64, every operation rounded once; the running sum is sequential because its rounding is observable
+ * (csrc/np_unwrap_kernels.hip.h: a row form for inner == 1 and a column form, the pointwise work on all lanes and one add per
+ * sample on one lane per line; neither limits len).  discont: numpy's default is period / 2; NaN is passed through (nothing is
+ * zeroed).  period: finite and > 0, else SSAMD_EINVAL (numpy would return NaN or sign-flipped intervals).  An empty extent does
+ * nothing.  SSAMD_ELIMIT beyond 2^40 samples, 2^26 - 1 lines (row form: inner == 1, lines = outer) or 2^24 - 1 workgroups
+ * (column form: outer x ceil(inner / 16)) -- a launch holds fewer than 2^32 threads.
+ * d_out may be d_p (in place); otherwise the buffers must not overlap.
+ * ssamd_np_unwrap: host buffers, synchronous.  ssamd_np_unwrap_device: device buffers, asynchronous on `stream`.
+ * ssamd_np_unwrap_xy / _xy_device: n maps [h][w]: axis 1 then axis 0 with discont = pi, period = 2 pi, two launches back to back
+ * on one stream, no host round trip between them.
+ * ssamd_np_unwrap_plan (needs no device): plan[0..7] = form (0 row, 1 column), samples (row form) or rows (column form) per
+ * chunk between two hand-overs of the carried state, lanes along the contiguous axis (64 / columns per workgroup), threads,
+ * workgroups, LDS bytes, samples per thread and chunk, lane groups per outer index; the same refusals as the operators. */
+int ssamd_np_unwrap(const double *p, long long outer, long long len, long long inner, double discont, double period, double *out,
+                    int device);
+int ssamd_np_unwrap_device(const double *d_p, long long outer, long long len, long long inner, double discont, double period,
+                           double *d_out, void *stream);
+int ssamd_np_unwrap_xy(const double *p, int n, int h, int w, double *out, int device);
+int ssamd_np_unwrap_xy_device(const double *d_p, int n, int h, int w, double *d_out, void *stream);
+int ssamd_np_unwrap_plan(long long outer, long long len, long long inner, int32_t *plan);
+
 /* ---- Fourier-transform profilometry: wrapped phase of a fringe image against a reference image ---------------- */
 /* The demodulation step of the reference's FTP pipeline (StereoFTP.getCloud, active.py:675-737; StereoFTP_PhaseOnly.getPhase,
  * :2012-2074), which is pure numpy there: gray = channel maximum (convertGrayscale), np.fft.fft along x of both images, the
@@ -263,7 +293,9 @@ int ssamd_iir_unwrap_device(const double *d_phase, int n, int h, int w, double t
  *                       !(f(s) - fmin < 0) && !(f(s) - fmax > 0): a NaN bound masks nothing on its side.
  *   out               : fp64 [h][w]: atan2(Im z, Re z), z = ghat * conj(g0hat); a row with an empty band is 0.0.
  *   unwrap            : 0 the wrapped phase; 1 ssamd_iir_unwrap's kernel runs on it (tau; same stream, no host round trip) and
- *                       out is what ssamd_iir_unwrap gives on the wrapped map, bit for bit; the unwrapper's checks and limits apply.
+ *                       out is what ssamd_iir_unwrap gives on the wrapped map, bit for bit; the unwrapper's checks and limits apply;
+ *                       2 ssamd_np_unwrap_xy's two launches run on it (same stream; tau is not read) and out is
+ *                       np.unwrap(np.unwrap(wrapped, discont=pi, axis=1), discont=pi, axis=0), bit for bit.  Anything else: SSAMD_EINVAL.
  * ssamd_ftp_phase: host buffers, synchronous (device as ssamd_iir_unwrap).  ssamd_ftp_phase_device: device image and output
  * buffers (fmin / fmax stay host arrays and are consumed before the call returns), asynchronous on `stream`. */
 #define SSAMD_FTP_MAX_W 8192
@@ -332,7 +364,8 @@ int ssamd_debug_gsw_sqrt(int n, float *out);
 #define SSAMD_K_ASW_EXACT 8  /* fp64 tie-break pass of ssamd_asw_exact* (fp64 Lab, filter, winners, eval, resolve, patch) */
 #define SSAMD_K_UNWRAP 9     /* phase unwrapping wavefront (iir_unwrap_kernel)                                     */
 #define SSAMD_K_FTP 10       /* Fourier-profilometry wrapped phase (ftp_phase_kernel)                              */
-#define SSAMD_K_COUNT 11
+#define SSAMD_K_NPUNWRAP 11  /* numpy's unwrap, one launch per scanned axis (np_unwrap_row_kernel / np_unwrap_col_kernel)   */
+#define SSAMD_K_COUNT 12
 int ssamd_profile_enable(int on);
 int ssamd_profile_reset(void);
 int ssamd_profile_read(double *ms /*[SSAMD_K_COUNT]*/, long long *launches /*[SSAMD_K_COUNT]*/);

@@ -17,10 +17,10 @@ if os.environ.get("SSAMD_LIB"):
         raise ImportError("SSAMD_LIB is an experiment hook: set SSAMD_EXPERIMENT=1 as well to load %s instead of the product "
                           "library" % os.environ["SSAMD_LIB"])
     LIB_PATH = os.environ["SSAMD_LIB"]
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 (K_LAB, K_ASW_AGG, K_ASW_FIN, K_GSW_AGG, K_GSW_FIN, K_REMAP, K_REPROJECT, K_ASW_ALT, K_ASW_EXACT, K_UNWRAP, K_FTP,
- K_COUNT) = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11
+ K_NPUNWRAP, K_COUNT) = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12
 
 _lib = None
 _u8p = ctypes.c_void_p
@@ -117,6 +117,17 @@ def lib():
     L.ssamd_ftp_phase_device.argtypes = [P, I, P, I, I, I, P, P, I, D, P, P]
     L.ssamd_ftp_band.restype = I
     L.ssamd_ftp_band.argtypes = [I, I, P, P, P, P]
+    LL = ctypes.c_longlong
+    L.ssamd_np_unwrap.restype = I
+    L.ssamd_np_unwrap.argtypes = [P, LL, LL, LL, D, D, P, I]
+    L.ssamd_np_unwrap_device.restype = I
+    L.ssamd_np_unwrap_device.argtypes = [P, LL, LL, LL, D, D, P, P]
+    L.ssamd_np_unwrap_xy.restype = I
+    L.ssamd_np_unwrap_xy.argtypes = [P, I, I, I, P, I]
+    L.ssamd_np_unwrap_xy_device.restype = I
+    L.ssamd_np_unwrap_xy_device.argtypes = [P, I, I, I, P, P]
+    L.ssamd_np_unwrap_plan.restype = I
+    L.ssamd_np_unwrap_plan.argtypes = [LL, LL, LL, ctypes.POINTER(ctypes.c_int32)]
     L.ssamd_debug_exact_queue.restype = I
     L.ssamd_debug_exact_queue.argtypes = [I, ctypes.c_longlong, P, P, P]
     L.ssamd_debug_libm.restype = I
@@ -221,3 +232,13 @@ def gsw_geometry(width, rows, winSize, maxDisparity, minDisparity):
     check(lib().ssamd_gsw_geometry(width, rows, winSize, maxDisparity, minDisparity, out))
     keys = ("tile_x", "chunk_d", "n_chunks", "threads", "lds_bytes", "grid_x", "grid_y", "grid_z", "strip_rows")
     return dict(zip(keys, list(out)))
+
+
+def np_unwrap_plan(outer, length, inner):
+    """Launch plan of ``unwrapping.unwrap`` for the geometry [outer][length][inner] (csrc/np_unwrap_plan.h; needs no device)."""
+    out = (ctypes.c_int32 * 8)()
+    check(lib().ssamd_np_unwrap_plan(outer, length, inner, out))
+    keys = ("form", "chunk", "lanes", "threads", "blocks", "lds_bytes", "per_thread", "groups")
+    d = dict(zip(keys, list(out)))
+    d["form"] = "column" if d["form"] else "row"
+    return d

@@ -7,11 +7,14 @@ Fourier-transform profilometry, executed by one HIP kernel on an AMD MI355X thro
 
     import simplestereo_amd as ss
     phase = ss.active.ftpPhase(imgObj, imgRef, fc, radius_factor=0.5, unwrap="iir", tau=0.8)
+    phase = ss.active.ftpPhase(imgObj, imgRef, fc, unwrap="numpy")      # the reference's default unwrapping
 
 ``ftpPhase`` is the demodulation of ``StereoFTP.getCloud`` (``active.py:675-737``; the same lines are
 ``StereoFTP_PhaseOnly.getPhase``, ``:2012-2074``): gray by the channel maximum, a row-wise FFT of the object image and of
 the (virtual) reference image, the per-row band-pass around the carrier ``fc``, an inverse FFT and
-``angle(ghat * conj(g0hat))`` -- optionally followed by the unwrapper the reference passes as ``unwrappingMethod``.
+``angle(ghat * conj(g0hat))`` -- optionally followed by the unwrapper the reference passes as ``unwrappingMethod``
+(``unwrap="iir"``) or by what it runs when none is passed, ``np.unwrap`` along x and then along y (``unwrap="numpy"``,
+``active.py:739-745``).
 It is NOT ``StereoFTP``: building the virtual reference image (``undistort``, ``projectPoints``, ``remap``), finding the
 central stripe, estimating ``fc`` and triangulating the phase into a cloud are cv2 calls in the reference and stay with
 the caller.
@@ -31,7 +34,7 @@ an image not [H, W] or [H, W, 3]                           ``ValueError``
 the two images differ in H or W                            ``ValueError``
 ``fc`` not a number or H numbers                           ``ValueError``
 ``radius_factor`` not a number                             ``ValueError``
-``unwrap`` neither ``None`` nor ``"iir"``                  ``ValueError``
+``unwrap`` not ``None``, ``"iir"`` or ``"numpy"``          ``ValueError``
 ``unwrap="iir"`` and ``tau`` not a number in [0, 1]        ``ValueError``
 W > ``MAX_WIDTH`` (8192)                                   ``ValueError``
 =========================================================  ==============
@@ -124,11 +127,13 @@ def ftpPhase(imgObj, imgRef, fc, radius_factor=0.5, unwrap=None, tau=1):
         every row.
     radius_factor : float, optional
         Half width of the pass band as a fraction of ``fc``.  Default 0.5.
-    unwrap : None or "iir", optional
+    unwrap : None, "iir" or "numpy", optional
         ``None``: the wrapped phase.  ``"iir"``: ``unwrapping.infiniteImpulseResponse`` of it with ``tau``, on the same
         stream without leaving the device; equal to calling the unwrapper on the wrapped result, bit for bit.
+        ``"numpy"``: ``unwrapping.unwrap2D`` of it, the reference's default (``np.unwrap`` with ``discont=np.pi`` along x,
+        then along y), likewise on the same stream and equal bit for bit to numpy's result on the wrapped map.
     tau : float, optional
-        The unwrapper's noise regularisation, 0 to 1 (only read with ``unwrap="iir"``).  Default 1.
+        The IIR unwrapper's noise regularisation, 0 to 1 (only read with ``unwrap="iir"``).  Default 1.
 
     Returns
     -------
@@ -146,16 +151,16 @@ def ftpPhase(imgObj, imgRef, fc, radius_factor=0.5, unwrap=None, tau=1):
     if (h, w) != (h2, w2):
         raise ValueError("imgObj and imgRef must have the same height and width (%dx%d, %dx%d)" % (h, w, h2, w2))
     fmin, fmax = _band(fc, radius_factor, h)
-    if unwrap is not None and not (isinstance(unwrap, str) and unwrap == "iir"):
-        raise ValueError('unwrap must be None or "iir"')
+    if unwrap is not None and not (isinstance(unwrap, str) and unwrap in ("iir", "numpy")):
+        raise ValueError('unwrap must be None, "iir" or "numpy"')
     t = 1.0
-    if unwrap is not None:
+    if unwrap == "iir":
         t = _c_double(tau)
         if t < 0 or t > 1:
             raise ValueError("Wrong tau value!")
     if w > MAX_WIDTH:
         raise ValueError("rows wider than %d columns are not supported (width %d)" % (MAX_WIDTH, w))
-    uw = 0 if unwrap is None else 1
+    uw = {None: 0, "iir": 1, "numpy": 2}[unwrap]
     if dev:
         import torch
         out = torch.empty((h, w), dtype=torch.float64, device=obj.device)

@@ -39,6 +39,7 @@ namespace ssamd {
 #include "asw_exact_kernels.hip.h"
 #include "rig_kernels.hip.h"
 #include "unwrap_kernels.hip.h"
+#include "np_unwrap_kernels.hip.h"
 #include "ftp_kernels.hip.h"
 
 using namespace ssamd;
@@ -66,6 +67,7 @@ int fail(int code, const char *fmt, ...)
 #include "asw_plan.h"
 #include "gsw_plan.h"
 #include "ftp_plan.h"
+#include "np_unwrap_plan.h"
 
 // Experiment / test hooks (declared in ssamd_options.h).  The SSAMD_* environment variables are read ONCE, when
 // the library is loaded; afterwards the table only changes through ssamd_set_option (tests, tools).  The host path of an operator
@@ -1496,7 +1498,7 @@ const char *ssamd_kernel_name(int slot)
                                                "asw finalize (wta_decode / lr_check_fill)",
                                                "gsw_aggregate_kernel", "gsw finalize (lr_check_fill)", "remap_bgr_kernel", "reproject_kernel",
                                                "asw_alt_fill_kernel", "asw fp64 tie-break pass (bgr2lab_f64_pair + asw_exact_winners / _eval / _resolve / _patch kernels)",
-                                               "iir_unwrap_kernel", "ftp_phase_kernel"};
+                                               "iir_unwrap_kernel", "ftp_phase_kernel", "np_unwrap_row_kernel / np_unwrap_col_kernel"};
     return (slot >= 0 && slot < SSAMD_K_COUNT) ? names[slot] : "";
 }
 
@@ -1927,6 +1929,130 @@ int ssamd_iir_unwrap_device(const double *d_phase, int n, int h, int w, double t
 }
 
 namespace {
+// np.unwrap on the geometry [outer][len][inner] (np_unwrap_plan.h): the checks shared by the host and the device entry points
+int npu_check(long long outer, long long len, long long inner, double period, NpuPlan &plan)
+{
+    if (!(period > 0) || !std::isfinite(period)) return fail(SSAMD_EINVAL, "period must be a finite positive number");
+    switch (npu_plan(outer, len, inner, plan)) {
+    case NPU_OK: return SSAMD_OK;
+    case NPU_NEGATIVE: return fail(SSAMD_EINVAL, "Wrong phase dimensions!");
+    case NPU_TOO_MANY_ELEMS: return fail(SSAMD_ELIMIT, "more than 2^40 phase samples (%lld x %lld x %lld)", outer, len, inner);
+    default:
+        return fail(SSAMD_ELIMIT, "more than %lld %s to scan (%lld x %lld): one launch holds fewer than 2^32 threads",
+                    NPU_MAX_LAUNCH_THREADS / plan.threads, plan.form == 0 ? "lines" : "groups of 16 columns", outer, inner);
+    }
+}
+
+// one scan; d_out may be d_p (the kernels work in place)
+int npu_launch(Ctx &c, const NpuPlan &plan, const double *d_p, long long len, long long inner, double discont, double period,
+               double *d_out, hipStream_t s)
+{
+    if (plan.blocks == 0) return SSAMD_OK;
+    const double hi = period / 2, lo = -hi;
+    Timed t(c, s, SSAMD_K_NPUNWRAP);
+    if (plan.form == 0)
+        hipLaunchKernelGGL(np_unwrap_row_kernel, dim3((unsigned)plan.blocks), dim3(plan.threads), 0, s, d_p, d_out, len, discont, period,
+                           hi, lo);
+    else
+        hipLaunchKernelGGL(np_unwrap_col_kernel, dim3((unsigned)plan.blocks), dim3(plan.threads), 0, s, d_p, d_out, len, inner,
+                           plan.groups, discont, period, hi, lo);
+    HIP_TRY(hipGetLastError());
+    return SSAMD_OK;
+}
+
+// the reference's default composition (active.py:739-745) on n maps [h][w]: along x (axis 1), then along y (axis 0), discont = pi
+struct NpuXY { NpuPlan x, y; };
+int npu_xy_check(int n, int h, int w, NpuXY &q)
+{
+    if (n < 0 || h < 0 || w < 0) return fail(SSAMD_EINVAL, "Wrong phase dimensions!");
+    int rc = npu_check((long long)n * h, w, 1, 2 * M_PI, q.x);
+    return rc ? rc : npu_check(n, h, w, 2 * M_PI, q.y);
+}
+int npu_xy_launch(Ctx &c, const NpuXY &q, const double *d_p, int h, int w, double *d_out, hipStream_t s)
+{
+    int rc = npu_launch(c, q.x, d_p, w, 1, M_PI, 2 * M_PI, d_out, s);
+    return rc ? rc : npu_launch(c, q.y, d_out, h, w, M_PI, 2 * M_PI, d_out, s);
+}
+
+// host buffers through the unwrapper's staging pair
+extern "C++" {
+template <class Launch>      // int launch(Ctx &, const double *d_p, double *d_out, hipStream_t)
+int npu_host(const double *p, double *out, size_t count, int device, Launch launch)
+{
+    CtxLock c;
+    int rc = get_ctx(device, c);
+    if (rc) return rc;
+    const size_t bytes = count * sizeof(double);
+    if ((rc = c->uwIn.reserve(bytes)) || (rc = c->uwOut.reserve(bytes))) return rc;
+    hipStream_t s = c->stream;
+    ScratchOrder order(*c, s);
+    HIP_TRY(hipMemcpyAsync(c->uwIn.ptr, p, bytes, hipMemcpyHostToDevice, s));
+    if ((rc = launch(*c, (const double *)c->uwIn.ptr, (double *)c->uwOut.ptr, s))) return rc;
+    HIP_TRY(hipMemcpyAsync(out, c->uwOut.ptr, bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return SSAMD_OK;
+}
+}  // extern "C++"
+}  // namespace
+
+int ssamd_np_unwrap_plan(long long outer, long long len, long long inner, int32_t *plan)
+{
+    if (!plan) return fail(SSAMD_EINVAL, "NULL buffer");
+    NpuPlan q;
+    int rc = npu_check(outer, len, inner, 1.0, q);
+    if (rc) return rc;
+    const int32_t v[8] = {q.form, q.chunk, q.lanes, q.threads, (int32_t)q.blocks, q.lds_bytes, q.per_thread, (int32_t)q.groups};
+    std::copy(v, v + 8, plan);
+    return SSAMD_OK;
+}
+
+int ssamd_np_unwrap(const double *p, long long outer, long long len, long long inner, double discont, double period, double *out,
+                    int device)
+{
+    NpuPlan q;
+    int rc = npu_check(outer, len, inner, period, q);
+    if (rc || q.blocks == 0) return rc;
+    if (!p || !out) return fail(SSAMD_EINVAL, "NULL buffer");
+    return npu_host(p, out, (size_t)outer * len * inner, device, [&](Ctx &c, const double *d_p, double *d_out, hipStream_t s) {
+        return npu_launch(c, q, d_p, len, inner, discont, period, d_out, s);
+    });
+}
+
+int ssamd_np_unwrap_device(const double *d_p, long long outer, long long len, long long inner, double discont, double period,
+                           double *d_out, void *stream)
+{
+    NpuPlan q;
+    int rc = npu_check(outer, len, inner, period, q);
+    if (rc || q.blocks == 0) return rc;
+    if (!d_p || !d_out) return fail(SSAMD_EINVAL, "NULL buffer");
+    CtxLock c;
+    if ((rc = get_ctx(-1, c))) return rc;
+    return npu_launch(*c, q, d_p, len, inner, discont, period, d_out, (hipStream_t)stream);
+}
+
+int ssamd_np_unwrap_xy(const double *p, int n, int h, int w, double *out, int device)
+{
+    NpuXY q;
+    int rc = npu_xy_check(n, h, w, q);
+    if (rc || q.y.blocks == 0) return rc;
+    if (!p || !out) return fail(SSAMD_EINVAL, "NULL buffer");
+    return npu_host(p, out, (size_t)n * h * w, device, [&](Ctx &c, const double *d_p, double *d_out, hipStream_t s) {
+        return npu_xy_launch(c, q, d_p, h, w, d_out, s);
+    });
+}
+
+int ssamd_np_unwrap_xy_device(const double *d_p, int n, int h, int w, double *d_out, void *stream)
+{
+    NpuXY q;
+    int rc = npu_xy_check(n, h, w, q);
+    if (rc || q.y.blocks == 0) return rc;
+    if (!d_p || !d_out) return fail(SSAMD_EINVAL, "NULL buffer");
+    CtxLock c;
+    if ((rc = get_ctx(-1, c))) return rc;
+    return npu_xy_launch(*c, q, d_p, h, w, d_out, (hipStream_t)stream);
+}
+
+namespace {
 // band planning, table and launches of ssamd_ftp_phase*; the caller holds the context and has ordered the scratch (ScratchOrder)
 static_assert(FTP_MAX_W == SSAMD_FTP_MAX_W, "ssamd.h states the width limit of ftp_plan.h");
 int ftp_check(int ch_obj, int ch_ref, int h, int w, const double *fmin, const double *fmax, int unwrap, double tau)
@@ -1934,9 +2060,13 @@ int ftp_check(int ch_obj, int ch_ref, int h, int w, const double *fmin, const do
     if (h <= 0 || w <= 0) return fail(SSAMD_EINVAL, "Wrong image dimensions!");
     if ((ch_obj != 1 && ch_obj != 3) || (ch_ref != 1 && ch_ref != 3)) return fail(SSAMD_EINVAL, "images must have 1 or 3 channels");
     if (!fmin || !fmax) return fail(SSAMD_EINVAL, "NULL band bounds");
-    if (unwrap != 0 && unwrap != 1) return fail(SSAMD_EINVAL, "unwrap must be 0 or 1");
+    if (unwrap < 0 || unwrap > 2) return fail(SSAMD_EINVAL, "unwrap must be 0, 1 or 2");
     if (w > FTP_MAX_W) return fail(SSAMD_ELIMIT, "rows wider than %d columns are not supported (width %d)", FTP_MAX_W, w);
-    return unwrap ? unwrap_check(1, h, w, tau) : SSAMD_OK;
+    if (unwrap == 2) {                                   // tau is not read
+        NpuXY q;
+        return npu_xy_check(1, h, w, q);
+    }
+    return unwrap == 1 ? unwrap_check(1, h, w, tau) : SSAMD_OK;
 }
 
 int ftp_twiddles(Ctx &c, int w, hipStream_t s, const double2 **tw)
@@ -1985,7 +2115,7 @@ int ftp_launch(Ctx &c, const uint8_t *d_obj, int ch_obj, const uint8_t *d_ref, i
     const double2 *tw = nullptr;
     if ((rc = ftp_twiddles(c, w, s, &tw))) return rc;
     double *d_phase = d_out;
-    if (unwrap) {
+    if (unwrap == 1) {                                   // the wavefront kernel does not work in place
         if ((rc = c.ftpPhase.reserve((size_t)h * w * sizeof(double)))) return rc;
         d_phase = (double *)c.ftpPhase.ptr;
     }
@@ -2007,6 +2137,11 @@ int ftp_launch(Ctx &c, const uint8_t *d_obj, int ch_obj, const uint8_t *d_ref, i
     default: rc = launch(&ftp_phase_kernel<8>); break;
     }
     if (rc) return rc;
+    if (unwrap == 2) {
+        NpuXY q;
+        if ((rc = npu_xy_check(1, h, w, q))) return rc;  // cannot fail: ftp_check has asked before anything was enqueued
+        return npu_xy_launch(c, q, d_out, h, w, d_out, s);
+    }
     return unwrap ? unwrap_launch(c, d_phase, 1, h, w, tau, d_out, s) : SSAMD_OK;
 }
 }  // namespace

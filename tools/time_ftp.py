@@ -7,6 +7,12 @@ For 1920x1080 and 4096x2160 (fc = 0.05, radius_factor = 0.5, synthetic fringes),
   kernel        ftp_phase_kernel alone (HIP events around the launch: ssamd_profile_*)
   device call   ftpPhase on uint8 tensors already in HBM (torch events around the call: band planning, band upload, kernel)
   device+iir    the same with unwrap="iir" (the unwrap kernel on top, same stream)
+  device+numpy  the same with unwrap="numpy" (np.unwrap along x, then along y: two scan launches on top, same stream)
+  unwrap        ss.unwrapping.unwrap of the wrapped map along axis 1 (row form) and along axis 0 (column form), and unwrap2D
+                (both), on a tensor in HBM (torch events around the call; the scan kernel alone by ssamd_profile_*), each equal
+                to numpy's result bit for bit; unwrap2D also on a steep noisy ramp, where every other sample jumps
+  host unwrap   the composition unwrap="numpy" replaces: download of the fp64 map, two np.unwrap calls, upload (host clock
+                around work that ends in a synchronise)
   host call     ftpPhase on numpy arrays (uploads, kernel, download, synchronous; host clock)
   numpy         fft / mask / ifft / angle in numpy on the host (host clock)
   torch.fft     max over channels, torch.fft.fft, mask, ifft, angle on the device (torch events), fp64 like the kernel
@@ -107,6 +113,40 @@ def main():
         t_kernel = statistics.median(kern)
         t_dev = median_events(lambda: ss.active.ftpPhase(tobj, tref, fc, rf))
         t_iir = median_events(lambda: ss.active.ftpPhase(tobj, tref, fc, rf, unwrap="iir", tau=0.8))
+        t_np = median_events(lambda: ss.active.ftpPhase(tobj, tref, fc, rf, unwrap="numpy"))
+        t_ux = median_events(lambda: ss.unwrapping.unwrap(got, axis=1))
+        t_uy = median_events(lambda: ss.unwrapping.unwrap(got, axis=0))
+        t_uxy = median_events(lambda: ss.unwrapping.unwrap2D(got))
+        lib.ssamd_profile_enable(1)
+        scan = {0: [], 1: []}
+        for _ in range(args.reps):
+            for axis in (0, 1):
+                lib.ssamd_profile_reset()
+                ss.unwrapping.unwrap(got, axis=axis)
+                ms, n = _native.profile_read()
+                assert n[_native.K_NPUNWRAP] == 1
+                scan[axis].append(ms[_native.K_NPUNWRAP])
+        lib.ssamd_profile_enable(0)
+        k_ux, k_uy = statistics.median(scan[1]), statistics.median(scan[0])
+        yy, xx = np.mgrid[0:h, 0:w]
+        steep = torch.from_numpy(np.angle(np.exp(1j * (2.9 * (xx + yy) + np.random.default_rng(2).normal(0, 0.1, (h, w)))))).cuda()
+        t_steep = median_events(lambda: ss.unwrapping.unwrap2D(steep))
+        assert np.array_equal(ss.unwrapping.unwrap2D(steep).cpu().numpy().view(np.uint64),
+                              np.unwrap(np.unwrap(steep.cpu().numpy(), axis=1), axis=0).view(np.uint64))
+
+        def host_composition():
+            wrapped = got.cpu().numpy()
+            unwrapped = np.unwrap(np.unwrap(wrapped, discont=np.pi, axis=1), discont=np.pi, axis=0)
+            up = torch.from_numpy(unwrapped).cuda()
+            torch.cuda.synchronize()
+            return unwrapped, up
+        t_hostuw = median_clock(host_composition, warm=1)
+        want = host_composition()[0]
+        same = all(np.array_equal(a.cpu().numpy().view(np.uint64), b.view(np.uint64)) for a, b in (
+            (ss.unwrapping.unwrap2D(got), want), (ss.active.ftpPhase(tobj, tref, fc, rf, unwrap="numpy"), want),
+            (ss.unwrapping.unwrap(got, axis=1), np.unwrap(got.cpu().numpy(), axis=1)),
+            (ss.unwrapping.unwrap(got, axis=0), np.unwrap(got.cpu().numpy(), axis=0))))
+        assert same, "the device unwrap differs from np.unwrap"
         t_host = median_clock(lambda: ss.active.ftpPhase(obj, ref, fc, rf))
         t_numpy = median_clock(lambda: numpy_way(obj, ref, fc, rf), warm=1)
 
@@ -127,14 +167,21 @@ def main():
                   "  kernel alone (ftp_phase_kernel)        %9.3f   (%.2f fp64 TFMA/s of the %.2e FMAs the two passes need)"
                   % (t_kernel, fma / t_kernel * 1e-9, fma),
                   "  device-tensor call                     %9.3f" % t_dev,
-                  "  device-tensor call, unwrap=\"iir\"       %9.3f" % t_iir,
+                  "  device-tensor call, unwrap=\"iir\"       %9.3f   (the unwrapper adds %.3f)" % (t_iir, t_iir - t_dev),
+                  "  device-tensor call, unwrap=\"numpy\"     %9.3f   (the unwrapper adds %.3f)" % (t_np, t_np - t_dev),
+                  "  unwrapping.unwrap axis=1 (row form)    %9.3f   (kernel alone %.3f: %.2f TB/s of the 16 bytes per sample it moves)"
+                  % (t_ux, k_ux, 16.0 * h * w / k_ux * 1e-9),
+                  "  unwrapping.unwrap axis=0 (column form) %9.3f   (kernel alone %.3f: %.2f TB/s)" % (t_uy, k_uy, 16.0 * h * w / k_uy * 1e-9),
+                  "  unwrapping.unwrap2D (both)             %9.3f" % t_uxy,
+                  "  unwrapping.unwrap2D, steep noisy ramp  %9.3f   (a jump at about every other sample: the worst case)" % t_steep,
+                  "  download + 2 np.unwrap + upload (host) %9.3f   (what unwrap=\"numpy\" replaces; results equal bit for bit)" % t_hostuw,
                   "  host-array call (copies included)      %9.3f" % t_host,
                   "  numpy on the host (the reference's way)%9.3f" % t_numpy,
                   "  torch.fft composition on the device    %9.3f" % t_torch,
                   "  largest angle between the kernel's map and numpy's %.2e, torch.fft's %.2e"
                   % (angle_between(got.cpu().numpy(), numpy_way(obj, ref, fc, rf)),
                      angle_between(got.cpu().numpy(), torch_way().cpu().numpy()))]
-        print("\n".join(lines[-9:]), flush=True)
+        print("\n".join(lines[-15:]), flush=True)
     text = "\n".join(lines) + "\n"
     if args.out:
         with open(args.out, "w") as f:
