@@ -209,7 +209,6 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(
     u64 *const bestL = reinterpret_cast<u64 *>(smem + g.off_bestL);
     u64 *const bestR = reinterpret_cast<u64 *>(smem + g.off_bestR);
     float4 *const cenLab = reinterpret_cast<float4 *>(smem + g.off_cen);
-    float *const proxS = reinterpret_cast<float *>(smem + g.off_prox);
 
     const int tid = threadIdx.x, nthr = blockDim.x;
     const int W = A.W, win = CG ? AswPipeTile<SLC, SRC, SEC>::id.win : A.win, p = CG ? AswPipeTile<SLC, SRC, SEC>::id.win / 2 : A.pad;
@@ -254,12 +253,12 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(
 
     // ---- build pieces.  Every thread index they use is re-derived from an opaque copy of threadIdx.x so that
     //      nothing of a build stays live across the aggregation (168-VGPR budget, no scratch).
-    // pixels (and the proximity row) of window row i -> staging buffer i & 1
+    // pixels of window row i -> staging buffer i & 1  (the proximity row is not staged: build_weights reads A.prox with scalar
+    // loads; AswGeom::off_prox stays planned for the kernels that share the layout)
     auto stage_row = [&](int i) {
         int tids = threadIdx.x;
         asm volatile("" : "+v"(tids));
         const int buf = i & 1, r = y - p + i;
-        for (int k = tids; k < win; k += nthr) proxS[buf * win + k] = A.prox[i * win + k];
         const PixRec *const rowL = A.recL + (size_t)r * W;
         const PixRec *const rowR = A.recR + (size_t)r * W;
         for (int k = tids; k < nL + nR; k += nthr) {
@@ -318,88 +317,93 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(
                                                  (__attribute__((address_space(3))) void *)(dst + k), 16, 0, 0);
     };
     // support weights of window row i, tap columns [jb, je), into weight buffer rows rb.. (_passive.cpp:47-50, 71-74;
-    // exp(-dist/gammaC) = exp2(dist*kC)).  One thread per window centre, all columns of the chunk: batches of ASW_WB
-    // independent chains walking running pointers; tap columns outside the image are staged with L = +inf and get weight +0
-    // (centres outside the image only feed candidates the winner-take-all never looks at).
+    // exp(-dist/gammaC) = exp2(dist*kC)); tap columns outside the image are staged with L = +inf and get weight +0 (centres
+    // outside the image only feed candidates the winner-take-all never looks at).
+    // The centres are dealt in CENTRE-WAVES of 64, left ones first, and a wave builds whole centre-waves: it never mixes left
+    // and right centres, so the staged pixel row, the weight row and its stride are scalars (compile-time strides in the
+    // static instantiations: the ASW_WB stores of a batch take immediate offsets from one address), every lane has the same
+    // [jb, je) and the trip state lives in scalar registers, and the proximity weight of a tap column is a scalar load from
+    // A.prox.  Batches of ASW_WB independent chains, then a straight-line remainder of exactly (je - jb) % ASW_WB weights
+    // picked by a scalar branch: no clamped index, no weight computed twice.
     auto build_weights = [&](int i, int jb, int je, int rb) {
+        static_assert(ASW_WB == 4, "the remainder below is written out for batches of four");
+        typedef const __attribute__((address_space(4))) float cfloat;      // read-only for the whole launch: scalar loads
         int tidw = threadIdx.x;
         asm volatile("" : "+v"(tidw));
+        const int wave = __builtin_amdgcn_readfirstlane(tidw >> 6), lane = tidw & 63;
+        // (Tx = SL and nRc = SR - 1 in the plain-row layout, asw_layout_e: the static strides name them and the thread count)
+        constexpr int NTHR = STATIC ? asw_cx_round_up((SLC / ASW_RX) * ((SRC - SLC) / ASW_RD), 64) : 0;
+        static_assert(!STATIC || (SG.Tx == SLC && SG.nRc == SRC - 1 && SG.threads == NTHR), "the strides name the centres and the threads");
+        const int TxB = STATIC ? SLC : Tx, nRcB = STATIC ? SRC - 1 : nRc, nw = (STATIC ? NTHR : nthr) >> 6;
+        const int nLw = (TxB + 63) >> 6, ncw = nLw + ((nRcB + 63) >> 6);
         const float4 *const labLc = labL + (i & 1) * nL, *const labRc = labR + (i & 1) * nR;
-        const float *const prow = proxS + (i & 1) * win;
-        const int ncen = Tx + nRc;
-        // tasks: one centre per thread with all columns of the chunk while whole rounds of nthr centres last; the
-        // centres left over (fewer than nthr) are cut into column segments so that the last round is spread over
-        // the threads instead of leaving most of them idle behind a few (tiles with more centres than threads)
-        const int full = ncen / nthr * nthr, rest = ncen - full;
+        cfloat *const prow = reinterpret_cast<cfloat *>(reinterpret_cast<uintptr_t>(A.prox)) + i * win;
+        // N weights of one centre: tap columns sp[0..N), proximity weights pp[0..N), into wp[0], wp[stride], ...
+        auto batch = [&](auto n_, const float4 &cen, const float4 *sp, cfloat *pp, float *wp, int stride) {
+            constexpr int N = decltype(n_)::value;
+            float4 tp[N];
+            float pr[N], wv[N];
+#pragma unroll
+            for (int u = 0; u < N; ++u) { tp[u] = sp[u]; pr[u] = pp[u]; }
+#pragma unroll
+            for (int u = 0; u < N; ++u) {
+                asm volatile("" ::"v"(tp[u].w));     // keeps the read a ds_read_b128 (4 LDS cycles; the 12-byte form takes 8)
+                const float dL = tp[u].x - cen.x, da = tp[u].y - cen.y, db = tp[u].z - cen.z;
+                wv[u] = fmaf(db, db, fmaf(da, da, dL * dL));
+            }
+#pragma unroll
+            for (int u = 0; u < N; ++u) wv[u] = __builtin_amdgcn_sqrtf(wv[u]);
+#pragma unroll
+            for (int u = 0; u < N; ++u) wv[u] = asw_weight_finish(wv[u], A.kC, pr[u]);
+#pragma unroll
+            for (int u = 0; u < N; ++u) wp[u * stride] = wv[u];
+        };
+        // centre cc (this lane's) of the left / right centres, tap columns [jb_t, je_t)
+        auto build_side = [&](auto left_, int cc, int jb_t, int je_t) {
+            constexpr bool LEFT = decltype(left_)::value;
+            const int stride = LEFT ? (STATIC ? SLC : g.SL) : (STATIC ? SRC : SR);
+            if (cc >= (LEFT ? TxB : nRcB)) return;      // lanes past the last centre of the side
+            const float4 cen = cenLab[(LEFT ? 0 : TxB) + cc];
+            asm volatile("" ::"v"(cen.w));
+            const float4 *sp = (LEFT ? labLc : labRc) + cc + jb_t;
+            cfloat *pp = prow + jb_t;
+            float *wp = (LEFT ? wL : wR) + cc + (rb + jb_t - jb) * stride;
+            int j = jb_t;
+#pragma nounroll
+            for (; j + ASW_WB <= je_t; j += ASW_WB, sp += ASW_WB, pp += ASW_WB, wp += ASW_WB * stride)
+                batch(std::integral_constant<int, ASW_WB>{}, cen, sp, pp, wp, stride);
+            const int rem = je_t - j;
+            if (rem == 1) batch(std::integral_constant<int, 1>{}, cen, sp, pp, wp, stride);
+            else if (rem == 2) batch(std::integral_constant<int, 2>{}, cen, sp, pp, wp, stride);
+            else if (rem == 3) batch(std::integral_constant<int, 3>{}, cen, sp, pp, wp, stride);
+        };
+        // tasks: a wave takes whole centre-waves with all columns of the chunk while whole rounds of nw centre-waves last; the
+        // centre-waves left over are cut into column segments (multiples of ASW_WB) so that the last round is spread over the
+        // waves instead of leaving most of them idle behind a few (tiles with more centres than threads).  All of it is scalar
+        // arithmetic on a handful of small numbers: counted out, no division.
+        // (Headline tile: 7 centre-waves on 12 waves, so SIMD 3 builds one where the others build two.  Handing batches of centre-waves
+        // 4-6 to wave 7, and eight building waves of 60 / 53 lanes, were both measured slower: profiles/r07_pipe_build_uniform.txt.)
+        int full = 0;
+        while (full + nw <= ncw) full += nw;
+        const int rest = ncw - full;
         int slen = je - jb, nseg = 1;
         if (rest > 0 && full > 0) {
-            slen = max(ASW_WB, (je - jb + nthr / rest - 1) / (nthr / rest));
-            slen = (slen + ASW_WB - 1) / ASW_WB * ASW_WB;
-            nseg = (je - jb + slen - 1) / slen;
+            int per = 0;                                   // waves per left-over centre-wave
+            for (int a = rest; a <= nw; a += rest) ++per;
+            for (slen = ASW_WB; slen * per < je - jb;) slen += ASW_WB;
+            while (nseg * slen < je - jb) ++nseg;
         }
-        const int ntasks = full + rest * nseg;
-        for (int t = tidw; t < ntasks; t += nthr) {
-            int c = t, jb_t = jb, je_t = je;
+        for (int t = wave; t < full + rest * nseg; t += nw) {
+            int cw = t, jb_t = jb, je_t = je;
             if (t >= full && nseg > 1) {
-                const int q = t - full, sgm = q / rest;
-                c = full + q - sgm * rest;
+                int q = t - full, sgm = 0;
+                while (q >= rest) { q -= rest; ++sgm; }
+                cw = full + q;
                 jb_t = jb + sgm * slen;
                 je_t = min(je, jb_t + slen);
             }
-            const bool isL = c < Tx;
-            const int cc = isL ? c : c - Tx;
-            const float4 cen = cenLab[c];
-            const float4 *const seg = (isL ? labLc : labRc) + cc;
-            const int stride = isL ? g.SL : SR;
-            float *const wout = (isL ? wL : wR) + cc + (rb - jb) * stride;
-            int j = jb_t;
-            const float4 *sp = seg + j;
-            const float *pp = prow + j;
-            float *wp = wout + j * stride;
-            const int stride4 = ASW_WB * stride;
-            for (; j + ASW_WB <= je_t; j += ASW_WB, sp += ASW_WB, pp += ASW_WB, wp += stride4) {
-                float4 tp[ASW_WB];
-                float pr[ASW_WB], wv[ASW_WB];
-#pragma unroll
-                for (int u = 0; u < ASW_WB; ++u) { tp[u] = sp[u]; pr[u] = pp[u]; }
-#pragma unroll
-                for (int u = 0; u < ASW_WB; ++u) {
-                    asm volatile("" ::"v"(tp[u].w));     // keeps the read a ds_read_b128 (4 LDS cycles; the 12-byte form takes 8)
-                    const float dL = tp[u].x - cen.x, da = tp[u].y - cen.y, db = tp[u].z - cen.z;
-                    wv[u] = fmaf(db, db, fmaf(da, da, dL * dL));
-                }
-#pragma unroll
-                for (int u = 0; u < ASW_WB; ++u) wv[u] = __builtin_amdgcn_sqrtf(wv[u]);
-#pragma unroll
-                for (int u = 0; u < ASW_WB; ++u) wv[u] = asw_weight_finish(wv[u], A.kC, pr[u]);
-#pragma unroll
-                for (int u = 0; u < ASW_WB; ++u) wp[u * stride] = wv[u];
-            }
-            if (j < je_t) {
-                float4 tp[ASW_WB];
-                float pr[ASW_WB], wv[ASW_WB];
-#pragma unroll
-                for (int u = 0; u < ASW_WB; ++u) {
-                    const int jj = min(j + u, je_t - 1);
-                    tp[u] = seg[jj];
-                    pr[u] = prow[jj];
-                }
-#pragma unroll
-                for (int u = 0; u < ASW_WB; ++u) {
-                    asm volatile("" ::"v"(tp[u].w));
-                    const float dL = tp[u].x - cen.x, da = tp[u].y - cen.y, db = tp[u].z - cen.z;
-                    wv[u] = fmaf(db, db, fmaf(da, da, dL * dL));
-                }
-#pragma unroll
-                for (int u = 0; u < ASW_WB; ++u) wv[u] = __builtin_amdgcn_sqrtf(wv[u]);
-#pragma unroll
-                for (int u = 0; u < ASW_WB; ++u) wv[u] = asw_weight_finish(wv[u], A.kC, pr[u]);
-#pragma unroll
-                for (int u = 0; u < ASW_WB; ++u) {  // past the segment end the clamped tap is simply rewritten
-                    const int jj = min(j + u, je_t - 1);
-                    wout[jj * stride] = wv[u];
-                }
-            }
+            if (cw < nLw) build_side(std::true_type{}, 64 * cw + lane, jb_t, je_t);
+            else build_side(std::false_type{}, 64 * (cw - nLw) + lane, jb_t, je_t);
         }
     };
     auto chunk_end = [&](int c) { return c == NC - 1 ? win : (c + 1) * JC; };
@@ -411,8 +415,10 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(
         // issued after the staged pixels are in LDS (their global loads are waited for with vmcnt(0), which would
         // also wait for these); lands under the chunk's taps, complete at the next barrier
         if (c == 0 && more_rows && A.evol) load_e(i + 1);
-        if (c + 1 < NC) build_weights(i, (c + 1) * JC, chunk_end(c + 1), (cb ^ 1) * g.JCmax);
-        else if (more_rows) build_weights(i + 1, 0, chunk_end(0), (cb ^ 1) * g.JCmax);
+        if (c + 1 < NC || more_rows) {                 // (one call: one copy of the build per wave order)
+            const int cn = c + 1 < NC ? c + 1 : 0;
+            build_weights(c + 1 < NC ? i : i + 1, cn * JC, chunk_end(cn), (cb ^ 1) * g.JCmax);
+        }
         if (c >= 1 && more_rows && !A.evol) build_e(i + 1, (int)((long long)nE * (c - 1) / (NC - 1)), (int)((long long)nE * c / (NC - 1)));
     };
 

@@ -70,7 +70,8 @@ bool asw_layout_e(AswGeom &g, const PlanOptions &po, int win, int XG, int DG, si
         g.Se = 16 * ((DG + 3) / 4);
         g.emask = 0;
     }
-    // weight build balance: (centres x segments) tasks over the workgroup's threads
+    // weight build balance: (centres x segments) tasks over the workgroup's threads (asw_aggregate_kernel; the phase-shifted
+    // kernel deals whole waves of 64 centres itself and reads neither field)
     {
         const int ncen = g.Tx + g.nRc;
         int best_cost = 1 << 30;
@@ -97,7 +98,8 @@ bool asw_layout_e(AswGeom &g, const PlanOptions &po, int win, int XG, int DG, si
     g.off_bestL = take((size_t)g.Tx * 8);
     g.off_bestR = take((size_t)(g.nRc + 1) * 8);
     g.off_cen = take((size_t)(g.Tx + g.nRc) * 16);
-    g.off_prox = take((size_t)win * 4 * 2);      // one window row of proximity weights, double-buffered
+    g.off_prox = take((size_t)win * 4 * 2);      // one window row of proximity weights, double-buffered (asw_aggregate_kernel stages it; the
+                                                 // phase-shifted kernel reads A.prox with scalar loads and leaves the slot unused)
     g.lds_bytes_evol = (int)off;
     if (g.pipe) {
         // the staged colour bytes only feed the in-kernel e tiles: LAST in the layout, so that a launch that has the pre-computed
