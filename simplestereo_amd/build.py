@@ -25,7 +25,11 @@ def needs_build():
 # translation units: (source, extra flags).  The LLVM scheduling strategy is a per-translation-unit option and the kernel families
 # disagree on the best one (profiles/r05_llvm_sched_strategy_ab.txt), so two of them are compiled apart (round 5).
 UNITS = [("ssamd_api.hip", []),
-         ("asw_pipe_tu.hip", ["-mllvm", "--amdgpu-sched-strategy=max-memory-clause"]),
+         # (no machine-level hoisting out of loops: what it lifts out of the persistent kernel's item loop stays live through
+         #  the taps and costs scratch; the tap-step blocks are the same instructions either way, DESIGN 4.3.  Both depend on the
+         #  compiler: after a ROCm update run tools/kernel_resources.sh asw_pipe_tu.hip with these flags -- every stride-only
+         #  instantiation must show 0 scratch and <= 168 VGPRs -- and tools/isa_blocks.py on the step blocks.)
+         ("asw_pipe_tu.hip", ["-mllvm", "--amdgpu-sched-strategy=max-memory-clause", "-mllvm", "-disable-machine-licm"]),
          ("asw_wave6_tu.hip", ["-mllvm", "--amdgpu-sched-strategy=max-ilp"])]
 
 

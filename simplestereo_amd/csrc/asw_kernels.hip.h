@@ -110,7 +110,13 @@ struct AswArgs {
     float kC;                    // -log2(e)/gammaC
     AswExactQueue xq;            // exact mode: near-tie queue (entries == nullptr: off)
     AswGeom g;
+    // (behind the geometry: the members above keep their places in the kernel-argument segment of every kernel that takes this struct)
+    unsigned int *pq;            // phase-shifted kernel, persistent form (asw_pipe_kernel.hip.h): ASW_PQ_QUEUES ticket counters + the counter of
+                                 //   finished items, one per 128-byte line; nullptr: one workgroup per tile, the grid is the work
+    int pq_nx, pq_ny, pq_items;  // ... the grid the items stand for (x tiles, workgroup rows) and their number nx * ny * nchunks
 };
+static constexpr int ASW_PQ_QUEUES = 8;      // one per XCD: queue q holds the items q, q + 8, q + 16, ... (what one XCD gets from a plain launch)
+static constexpr int ASW_PQ_LINE = 32;       // counters are 32 dwords apart
 
 // ---- the phase-shifted kernel's tiles of the headline configurations as COMPILE-TIME geometry (round 6) ------------------------
 // asw_aggregate_pipe_kernel<.., SLC, SRC, SEC> used to take only its three LDS strides as constants and read the other ~30 geometry

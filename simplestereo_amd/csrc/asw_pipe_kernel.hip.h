@@ -186,8 +186,10 @@ __global__ __launch_bounds__(256) void asw_prepass_kernel(const AswPrepassArgs P
 // advanced once per trip: 3 address instructions per 8 steps instead of 24 (107 -> 104.4 VALU instructions per step).
 // CG (round 6): the static instantiation takes the WHOLE tile geometry and the window from compile-time constants (see AswPipeTile);
 // false = strides only (rounds 3-5).  Both are built so that they can be compared in one process (SSAMD_ASW_STATIC=2 / 1).
+// AswArgs must stay the kernel's ONLY parameter: the item loop reads it at offset 0 of the kernel-argument segment
+// (__builtin_amdgcn_kernarg_segment_ptr, see the loop at the end of the body).
 template <bool WITH_COSTS, int SLC = 0, int SRC = 0, int SEC = 0, bool CG = false>
-__global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(const AswArgs A)
+__global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(const AswArgs A0)
 {
     constexpr bool STATIC = SLC > 0;
     static_assert(!CG || STATIC, "compile-time geometry belongs to a static tile");
@@ -198,6 +200,14 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(
     // them: asw_pipe_geom_matches); the generic instantiation reads them from the arguments
     constexpr AswGeom SG = asw_pipe_geom_constexpr(AswPipeTile<SLC, SRC, SEC>::id);
     static_assert(!STATIC || (SG.SL == SLC && SG.SR == SRC && SG.Se == SEC), "the strides name the tile");
+    // Persistent form (A.pq != nullptr, see the loop behind this lambda): the ticket of the workgroup's NEXT item, drawn from queue
+    // pq_q under the current item and left in a dword of LDS the kernel has no other use for (AswGeom::off_prox)
+    uint32_t *const pq_next = reinterpret_cast<uint32_t *>(smem + (CG ? SG : A0.g).off_prox);
+    int pq_q = 0;
+    // One work item: the tile (ibx, iby, ibz) of a grid of inx tiles per row -- blockIdx and gridDim.x of the plain launch.  A `return`
+    // in here (and in asw_epilogue.inc) ends the item, not the kernel.  A: the kernel's arguments as the item reads them (see the loop).
+    auto run_item = [&](const AswArgs &A, const int ibx, const int iby, const int ibz, const int inx) __attribute__((always_inline)) {
+    const bool persist = A.pq != nullptr;
     const AswGeom &g = CG ? SG : A.g;
     float *const wL = reinterpret_cast<float *>(smem + g.off_wL);
     float *const wR = reinterpret_cast<float *>(smem + g.off_wR);
@@ -214,18 +224,29 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(
     const int W = A.W, win = CG ? AswPipeTile<SLC, SRC, SEC>::id.win : A.win, p = CG ? AswPipeTile<SLC, SRC, SEC>::id.win / 2 : A.pad;
     const int Tx = g.Tx, Dc = g.Dc, nL = g.nL, nR = g.nR, nRc = g.nRc, SR = g.SR, Se = g.Se;
     const int JC = g.JC, NC = g.NC;
-    int bx = blockIdx.x;                          // XCD-aware tile order, see asw_aggregate_kernel
-    if ((gridDim.x & 7) == 0) bx = (bx & 7) * (gridDim.x >> 3) + (bx >> 3);
+    // (the row stride as 64 bits, made here as a scalar pair: extended where a lane loop first needs it, inside the item loop the
+    //  product became a value of divergent control flow and took two vector registers through the taps)
+    size_t Wz = (size_t)W;
+    asm volatile("" : "+s"(Wz));
+    int bx = ibx;                                 // XCD-aware tile order, see asw_aggregate_kernel
+    if ((inx & 7) == 0) bx = (bx & 7) * (inx >> 3) + (bx >> 3);
     const int x0 = bx * Tx;
-    const int y = asw_out_row(A, blockIdx.y);
-    const int dlo = A.minD + blockIdx.z * Dc;
+    const int y = asw_out_row(A, iby);
+    const int dlo = A.minD + ibz * Dc;
     const int dhi = dlo + Dc - 1;
     if (min(x0 + Tx - 1, W - 1) - dlo < 0) {      // no candidate the reference evaluates in this tile
         if (A.disp)
             for (int k = threadIdx.x; k < Tx && x0 + k < W; k += blockDim.x)
-                A.disp[(size_t)(y - A.row0) * W + x0 + k] = (int16_t)(x0 + k);
+                A.disp[(size_t)(y - A.row0) * Wz + x0 + k] = (int16_t)(x0 + k);
+        if (persist) {
+            if (threadIdx.x == 0) *pq_next = atomicAdd(A.pq + pq_q * ASW_PQ_LINE, 1u);
+            __syncthreads();
+        }
         return;
     }
+    // the next ticket: asked for here, waited for behind the first staged row's loads (which are waited for anyway)
+    uint32_t pq_ticket = 0;
+    if (persist && threadIdx.x == 0) pq_ticket = atomicAdd(A.pq + pq_q * ASW_PQ_LINE, 1u);
     const int segL_lo = x0 - p, xrc_lo = x0 - dhi, segR_lo = xrc_lo - p;
     // which of the two orders this wave follows (0: build first): wave-uniform, kept in a scalar register
     const int phase = g.dephase ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8)) : 1;
@@ -243,7 +264,7 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(
         const int ccol = isL ? x0 + c : xrc_lo + (c - Tx);
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if ((unsigned)ccol < (unsigned)W) {
-            const PixRec q = (isL ? A.recL : A.recR)[(size_t)y * W + ccol];
+            const PixRec q = (isL ? A.recL : A.recR)[(size_t)y * Wz + ccol];
             v = make_float4(q.L, q.a, q.b, 1.f);
         }
         cenLab[c] = v;
@@ -259,8 +280,8 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(
         int tids = threadIdx.x;
         asm volatile("" : "+v"(tids));
         const int buf = i & 1, r = y - p + i;
-        const PixRec *const rowL = A.recL + (size_t)r * W;
-        const PixRec *const rowR = A.recR + (size_t)r * W;
+        const PixRec *const rowL = A.recL + (size_t)r * Wz;
+        const PixRec *const rowR = A.recR + (size_t)r * Wz;
         for (int k = tids; k < nL + nR; k += nthr) {
             const bool isL = k < nL;
             const int idx = isL ? k : k - nL;
@@ -308,7 +329,7 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(
         int tidd = threadIdx.x;
         asm volatile("" : "+v"(tidd));
         const int r = y - p + i;
-        const unsigned char *const src = A.evol + (((size_t)blockIdx.z * A.erows + (r - A.erow0)) * (size_t)A.evolW + x0) * Se;
+        const unsigned char *const src = A.evol + (((size_t)ibz * A.erows + (r - A.erow0)) * (size_t)A.evolW + x0) * Se;
         unsigned char *const dst = eT0 + (i & 1) * g.e_bytes;
         const int bytes = nL * Se, lane16 = (tidd & 63) * 16;
         for (int k = __builtin_amdgcn_readfirstlane(tidd >> 6) * 1024; k < bytes; k += (nthr >> 6) * 1024)
@@ -424,6 +445,7 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(
 
     // ---- prologue: first window row staged, its e tile and its first weight chunk built (not overlapped: 1 / win of the work)
     stage_row(i_lo);
+    if (persist && threadIdx.x == 0) *pq_next = pq_ticket;
     if (A.evol) load_e(i_lo);
     __syncthreads();
     if (!A.evol) build_e(i_lo, 0, nE);
@@ -552,8 +574,54 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(
 #define ASW_EPI_TID tid
 #define ASW_EPI_NTHR nthr
 #define ASW_EPI_SYNC() __syncthreads()
-#define ASW_EPI_ROW (size_t)(y - A.row0) * W
+#define ASW_EPI_ROW (size_t)(y - A.row0) * Wz
 #include "asw_epilogue.inc"
+    };
+
+    // Plain launch: the grid is the work, one trip.  Persistent launch (round 8): fewer workgroups than items; item id stands for the
+    // block (id % nx, id / nx % ny, id / (nx ny)) of the plain grid and goes through the same mapping, so every tile is computed by
+    // the same instructions as before.  Queue q holds the ids q, q + 8, ...: a workgroup draws tickets (one lane's atomicAdd, handed
+    // round through LDS) from the queue of its XCD, moves on to the next queue when one is exhausted -- a queue never refills, so it
+    // never looks back -- and ends behind the eighth.  Nobody waits for anybody: at most items + 8 tickets are drawn per workgroup.
+    int dead = 0;
+    if (A0.pq) {
+        uint32_t xcc;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+        pq_q = (int)(xcc & (ASW_PQ_QUEUES - 1));
+        if (threadIdx.x == 0) *pq_next = atomicAdd(A0.pq + pq_q * ASW_PQ_LINE, 1u);
+        __syncthreads();
+    }
+    for (;;) {
+        // Every item reads the arguments from the kernel-argument segment through a pointer the optimiser cannot see through: what
+        // an item keeps in scalar registers is then what the one-trip kernel kept, and nothing is carried round the loop for it
+        // (with the arguments hoisted out of the loop the kernel spilled scalars into the tap loop and vector registers to scratch).
+        typedef const __attribute__((address_space(4))) AswArgs *KernArgs;
+        uintptr_t ka = reinterpret_cast<uintptr_t>(__builtin_amdgcn_kernarg_segment_ptr());
+        asm volatile("" : "+s"(ka));
+        const AswArgs &A = *(const AswArgs *)reinterpret_cast<KernArgs>(ka);
+        const bool persist = A.pq != nullptr;
+        int ibx = blockIdx.x, iby = blockIdx.y, ibz = blockIdx.z, inx = gridDim.x;
+        if (persist) {
+            int item = pq_q + ASW_PQ_QUEUES * __builtin_amdgcn_readfirstlane((int)*pq_next);
+            while ((unsigned)item >= (unsigned)A.pq_items) {
+                if (++dead == ASW_PQ_QUEUES) return;
+                pq_q = (pq_q + 1) & (ASW_PQ_QUEUES - 1);
+                __syncthreads();       // every thread has read the ticket that is replaced now
+                if (threadIdx.x == 0) *pq_next = atomicAdd(A.pq + pq_q * ASW_PQ_LINE, 1u);
+                __syncthreads();
+                item = pq_q + ASW_PQ_QUEUES * __builtin_amdgcn_readfirstlane((int)*pq_next);
+            }
+            __syncthreads();           // the last item's reads of bestL / bestR and of the ticket come before this item's writes
+            inx = A.pq_nx;
+            const int row = item / inx;
+            ibx = item - row * inx;
+            ibz = row / A.pq_ny;
+            iby = row - ibz * A.pq_ny;
+        }
+        run_item(A, ibx, iby, ibz, inx);
+        if (!persist) return;
+        if (threadIdx.x == 0) atomicAdd(reinterpret_cast<unsigned long long *>(A.pq + ASW_PQ_QUEUES * ASW_PQ_LINE), 1ull);      // items finished (ssamd_counter "pipe_persist_items")
+    }
 }
 
 }  // namespace ssamd

@@ -2,6 +2,8 @@
 // -mllvm --amdgpu-sched-strategy=max-memory-clause (simplestereo_amd/build.py): - 0.4 ... 1.1 % on configs 3 / 5, - 0.4 ... 2 % on
 // config 2 against the default strategy, maps bit-identical (profiles/r05_llvm_sched_strategy_ab.txt).  A strategy is a
 // per-translation-unit option; the other kernel families lose with this one.
+// Also with -mllvm -disable-machine-licm (round 8): the kernel body is a loop over work items, and the thread-constant values the
+// machine-level hoisting lifts in front of that loop stay live through the tap loop (168 VGPRs: they went to scratch).
 #define SSAMD_KERNEL_TU 1
 #include <hip/hip_runtime.h>
 #include "asw_pipe_kernel.hip.h"

@@ -195,6 +195,7 @@ struct Ctx {
     hipStream_t stream = nullptr;       // used by the host-buffer entry points
     DevBuf imgL, imgR, recL, recR, keyL, keyR, disp, costs, lab, altq, evol, altdisp;
     DevBuf xlabL, xlabR, xflags, xqueue, xcost, xslots, xctr, xraw, xwtab;      // fp64 tie-break pass (asw_exact_kernels.hip.h)
+    DevBuf pq;                          // ticket counters of the persistent phase-shifted launch (asw_launch_pipe), zeroed before each one
     DevBuf uwIn, uwOut;                 // host-buffer phase unwrapping (unwrap_kernels.hip.h)
     DevBuf ftpBand, ftpPhase;           // FTP phase (ftp_kernels.hip.h): kept bins per row; the wrapped map on its way to the unwrapper
     std::map<int, DevBuf> ftpTabs;      // twiddle table e^{2 pi i j / w} per width, built on the device
@@ -209,6 +210,7 @@ struct Ctx {
     long long evol_fallbacks = 0;       // calls that ran without the volume (in-kernel e tiles) or off the wave kernel for lack of memory
     long long tail_splits = 0;          // phase-shifted launches whose last partial round of workgroups ran as half-width tiles
     long long exact_calls = 0;          // ASW calls that ran the fp64 tie-break pass
+    long long persist_launches = 0;     // phase-shifted launches in the persistent form
     long long static_tile_mismatch = 0; // pipe launches whose strides named a static tile that the full geometry did not match
     Profile prof;
 };
@@ -964,12 +966,13 @@ int asw_launch_pipe(AswRun &r, const AswArgs &a, const dim3 &grid)
     // (tests/test_gpu_asw.py).  Worth ~4 % at 8.44 rounds, nothing beyond a few dozen; SSAMD_ASW_TAIL=0 / 1 forces.
     int rows_main = r.grows;
     AswGeom tail_g;
+    // workgroups in flight at a time: the device's CUs x the tile's residency (168 VGPRs -> three waves per SIMD;
+    // the tile's LDS).  One per CU for the 9- to 12-wave tiles of the headline configurations.
+    const int per_simd = (g.threads / 64 + 3) / 4;
+    const long long resident = std::max(1, std::min(3 / std::max(1, per_simd), (160 * 1024) / std::max(1, pipe_lds)));
+    const long long per_row = (long long)grid.x * g.nchunks, slots = (long long)c.cus * resident;
     if (!r.alternate && r.t.asw_tail != 0 && g.XG >= 4) {
-        // workgroups in flight at a time: the device's CUs x the tile's residency (168 VGPRs -> three waves per SIMD;
-        // the tile's LDS).  One per CU for the 9- to 12-wave tiles of the headline configurations.
-        const int per_simd = (g.threads / 64 + 3) / 4;
-        const long long resident = std::max(1, std::min(3 / std::max(1, per_simd), (160 * 1024) / std::max(1, pipe_lds)));
-        const long long per_row = (long long)grid.x * g.nchunks, n = per_row * r.grows, slots = (long long)c.cus * resident;
+        const long long n = per_row * r.grows;
         const long long full = n / slots, rem = n - full * slots;
         if (full >= 1 && rem > 0 && 2 * rem <= slots && (full < 32 || r.t.asw_tail > 0)) {
             const int rm = (int)(full * slots / per_row);
@@ -982,7 +985,32 @@ int asw_launch_pipe(AswRun &r, const AswArgs &a, const dim3 &grid)
             }
         }
     }
-    hipLaunchKernelGGL(pk, dim3(grid.x, rows_main, grid.z), dim3(g.threads), pipe_lds, r.s, a);
+    // The persistent form (round 8, asw_pipe_kernel.hip.h): as many workgroups as are resident at a time, each drawing the launch's
+    // tiles as items from eight queues.  What it recovers is the XCD whose tiles include the light left-border ones running dry
+    // about 12 % of the launch early (the dispatcher deals blocks to XCDs by id % 8 whatever their load: profiles/r08_xcd_dispatch.txt)
+    // and the round quantisation; what it costs is fixed (the memset, one exposed ticket).  Measured on the 120 x 196 tile
+    // (profiles/r08_pipe_persistent.txt): + 0.6 % at 8 full rounds, + 0.3 % at 16, nothing either way at 33.75, - 0.8 ... - 1.2 % at 67.5
+    // (1080p), - 1.5 % at 4096 x 2160.  The host picks it from 64 full rounds on: where it is measured to gain.  Between 34 and 64
+    // rounds nothing is measured and the launch stays the plain grid.  SSAMD_ASW_PERSIST=0 / n forces the plain grid /
+    // min(n, slots) workgroups.  Same tiles, same instructions.
+    const long long items = per_row * rows_main;
+    long long workers = r.t.asw_persist > 0 ? std::min<long long>(r.t.asw_persist, slots) : (r.t.asw_persist < 0 && items >= 64 * slots ? slots : 0);
+    workers = std::min(workers, items);
+    if (workers > 0 && items < (1ll << 30)) {
+        const size_t pq_bytes = (size_t)(ASW_PQ_QUEUES + 1) * ASW_PQ_LINE * 4;
+        if (!c.pq.ptr) {
+            if (int prc = c.pq.reserve(pq_bytes)) return prc;
+            HIP_TRY(hipMemsetAsync(c.pq.ptr, 0, pq_bytes, r.s));       // (the counter of finished items behind the queues' is never zeroed again)
+        }
+        HIP_TRY(hipMemsetAsync(c.pq.ptr, 0, (size_t)ASW_PQ_QUEUES * ASW_PQ_LINE * 4, r.s));
+        AswArgs pa = a;
+        pa.pq = (unsigned int *)c.pq.ptr;
+        pa.pq_nx = (int)grid.x; pa.pq_ny = rows_main; pa.pq_items = (int)items;
+        ++c.persist_launches;
+        hipLaunchKernelGGL(pk, dim3((unsigned)workers), dim3(g.threads), pipe_lds, r.s, pa);
+    } else {
+        hipLaunchKernelGGL(pk, dim3(grid.x, rows_main, grid.z), dim3(g.threads), pipe_lds, r.s, a);
+    }
     HIP_TRY(hipGetLastError());
     if (rows_main < r.grows) {
         ++c.tail_splits;
@@ -1533,6 +1561,16 @@ int ssamd_counter(int device, const char *name, long long *value)
     else if (n == "tail_splits") *value = c->tail_splits;
     else if (n == "exact_calls") *value = c->exact_calls;
     else if (n == "static_tile_mismatch") *value = c->static_tile_mismatch;
+    else if (n == "pipe_persist_launches") *value = c->persist_launches;
+    else if (n == "pipe_persist_items") {
+        // tiles finished by persistent phase-shifted launches on this device so far (counted on the device, once per finished item)
+        unsigned long long done = 0;
+        if (c->pq.ptr) {
+            HIP_TRY(hipDeviceSynchronize());
+            HIP_TRY(hipMemcpy(&done, (const unsigned int *)c->pq.ptr + ASW_PQ_QUEUES * ASW_PQ_LINE, sizeof(done), hipMemcpyDeviceToHost));
+        }
+        *value = (long long)done;
+    }
     else if (n == "exact_entries" || n == "exact_flagged_left" || n == "exact_flagged_right" || n == "exact_overflow" || n == "exact_raw_entries") {
         // of the LAST exact call on this device: candidates re-evaluated in fp64, pixels with near-ties, whether the queue overflowed
         unsigned int ctr[5] = {0, 0, 0, 0, 0};
