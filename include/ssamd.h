@@ -386,8 +386,7 @@ int ssamd_set_option(const char *name, const char *value);
  * synchronise the device): "exact_entries" candidates re-evaluated in fp64, "exact_flagged_left" / "exact_flagged_right"
  * pixels with near-ties, "exact_raw_entries" what the aggregation kernels of a merging call (several chunks / consistent) queued
  * against their tile-local winners before the filter, "exact_overflow" 1 when a candidate queue overflowed (the fp32 map was
- * kept); "static_tile_mismatch": SSAMD_ASW_STATIC=2 launches whose planned geometry did not equal a compile-time tile;
- * "pipe_persist_launches": phase-shifted launches in the persistent form (SSAMD_ASW_PERSIST), "pipe_persist_items": the tiles
+ * kept); "pipe_persist_launches": phase-shifted launches in the persistent form (SSAMD_ASW_PERSIST), "pipe_persist_items": the tiles
  * those launches finished, counted on the device once per tile (synchronises the device).
  * SSAMD_EINVAL for an unknown name. */
 int ssamd_counter(int device, const char *name, long long *value);

@@ -27,7 +27,7 @@ def needs_build():
 UNITS = [("ssamd_api.hip", []),
          # (no machine-level hoisting out of loops: what it lifts out of the persistent kernel's item loop stays live through
          #  the taps and costs scratch; the tap-step blocks are the same instructions either way, DESIGN 4.3.  Both depend on the
-         #  compiler: after a ROCm update run tools/kernel_resources.sh asw_pipe_tu.hip with these flags -- every stride-only
+         #  compiler: after a ROCm update run tools/kernel_resources.sh asw_pipe_tu.hip with these flags -- every
          #  instantiation must show 0 scratch and <= 168 VGPRs -- and tools/isa_blocks.py on the step blocks.)
          ("asw_pipe_tu.hip", ["-mllvm", "--amdgpu-sched-strategy=max-memory-clause", "-mllvm", "-disable-machine-licm"]),
          ("asw_wave6_tu.hip", ["-mllvm", "--amdgpu-sched-strategy=max-ilp"])]

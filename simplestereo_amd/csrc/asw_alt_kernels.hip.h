@@ -15,7 +15,7 @@
 // On Tsukuba about 10 % of all pixels need an evaluation, over about 4 candidates each; bad-1.0 against
 // the ground truth does not get worse.
 #pragma once
-#include "asw_kernels.hip.h"
+#include "asw_shared.hip.h"
 
 namespace ssamd {
 

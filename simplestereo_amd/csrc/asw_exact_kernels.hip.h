@@ -6,7 +6,7 @@
 // argmin the reference's wherever fp64 can tell the candidates apart:
 //
 //   1. (round 6) the aggregation kernels themselves, in their epilogue, queue every candidate that is a NEAR-TIE of its pixel's
-//      winner and flag the pixel (asw_exact_select / asw_exact_merge, asw_kernels.hip.h): the keys are still in registers and
+//      winner and flag the pixel (asw_exact_select / asw_exact_merge, asw_shared.hip.h): the keys are still in registers and
 //      the tile-local winners in LDS there.  Round 5 dumped the cost image of EVERY candidate to HBM (H*W*nD*4 bytes: 1.6 GB at
 //      1080p / 193, 9.1 GB at 4K) and re-read it in a flag kernel to find 0.006 % of it;
 //      -- directly when the workgroup's winner is final (one disparity chunk, no right pass), else into a RAW queue with their
@@ -30,7 +30,7 @@
 // more than the near-tie band from their winner although it wins in fp64 (none seen; the band grows with the window,
 // ssamd_api.hip), and a queue overflow (counted, reported, the fp32 map is kept).
 #pragma once
-#include "asw_kernels.hip.h"
+#include "asw_shared.hip.h"
 #include "lab_kernels.hip.h"
 #include "glibc_math.hip.h"
 

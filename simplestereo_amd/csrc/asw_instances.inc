@@ -11,11 +11,6 @@ SSAMD_PIPE_INSTANCE(true, 120, 316, 208)
 SSAMD_PIPE_INSTANCE(true, 88, 348, 272)
 SSAMD_PIPE_INSTANCE(true, 216, 284, 80)
 #endif
-#ifdef SSAMD_PIPE_INSTANCE_CG          // ... with the whole tile geometry as compile-time constants (round 6)
-SSAMD_PIPE_INSTANCE_CG(false, 120, 316, 208)
-SSAMD_PIPE_INSTANCE_CG(false, 88, 348, 272)
-SSAMD_PIPE_INSTANCE_CG(false, 216, 284, 80)
-#endif
 #ifdef SSAMD_WAVE6_INSTANCE
 SSAMD_WAVE6_INSTANCE(true, 0, false)
 SSAMD_WAVE6_INSTANCE(false, 0, false)

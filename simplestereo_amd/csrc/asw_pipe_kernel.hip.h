@@ -37,145 +37,9 @@
 // 0.37, LDS 55 % busy); see profiles/r02_*.  It also needs one running pointer per operand instead of three for
 // wR and no swizzle arithmetic.
 #pragma once
-#include "asw_kernels.hip.h"
-#ifndef SSAMD_KERNEL_TU
-#include "lab_kernels.hip.h"
-#endif
+#include "asw_shared.hip.h"
 
 namespace ssamd {
-
-#ifndef SSAMD_KERNEL_TU
-// K0e: the truncated absolute differences e[r][u][d] = min(40, |dB|+|dG|+|dR|) of L[r][u] and R[r][u-d]
-// (_passive.cpp:77-79) for every image row the launch touches, as bytes in exactly the layout of the kernel's e
-// tiles: [disparity chunk z][row][column u + pad][Se bytes = one dword per 4 disparities, padded].  e depends on
-// (r, u, d) only, so each value is needed by the up to winSize window rows of winSize output rows: built once here
-// (H*W*nD bytes: 0.4 GB at 1080p / 193, a 0.1 ms HBM-bound kernel) instead of winSize times inside the aggregation
-// kernel, whose workgroups then fetch their tiles with LDS-DMA (global_load_lds_dwordx4: no VALU work, no
-// registers).  Columns or disparities outside the image get 0; their taps carry weight 0.
-// Workgroup = one image row x 64 columns x one disparity chunk.  The pixels are staged in LDS (coalesced record
-// reads), every thread then produces whole dwords (4 disparities) of one column, and the 64 x Se byte block -- a
-// contiguous piece of the volume -- is written with consecutive lanes on consecutive dwords.
-static constexpr int TADV_COLS = 64;
-// One tile (bx, by, bz) of the volume.  BYTES: the pixels come straight from the caller's uint8 [H][W][3] images instead of the
-// records -- the volume then does not depend on the Lab conversion and both run in ONE launch (asw_prepass_kernel below).
-template <bool BYTES>
-__device__ __forceinline__ void asw_tad_tile(const void *__restrict__ srcL, const void *__restrict__ srcR, unsigned char *__restrict__ evol,
-                                             int W, int pad, int minD, int Dc, int Se, int erow0, int erows, int evolW, int rd, long long npix_total,
-                                             int bx, int by, int bz, char *smem)
-{
-    uint32_t *const sL = reinterpret_cast<uint32_t *>(smem);                 // [TADV_COLS]
-    uint32_t *const sR = sL + TADV_COLS;                                     // [TADV_COLS + Dc]: right columns u0 - dhi .. u0 + 63 - dlo
-    const int r = erow0 + by, z = bz, uc0 = bx * TADV_COLS;
-    const int P = Se >> 2, dlo = minD + z * Dc, dhi = dlo + Dc - 1;
-    const int u0 = uc0 - pad, xr0 = u0 - dhi;
-    auto pixel = [&](const void *src, int col) -> uint32_t {
-        const size_t q = (size_t)r * W + col;
-        if constexpr (BYTES) {
-            typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
-            const uint8_t *const b = reinterpret_cast<const uint8_t *>(src) + 3 * q;
-            // (the 4-byte read of the image's last pixel would run one byte past the buffer)
-            return (long long)q + 1 < npix_total ? (*reinterpret_cast<const u32_unaligned *>(b) & 0xffffffu)
-                                                 : ((uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16));
-        } else {
-            return reinterpret_cast<const PixRec *>(src)[q].bgrx;
-        }
-    };
-    for (int k = threadIdx.x; k < 2 * TADV_COLS + Dc; k += blockDim.x) {
-        const bool isL = k < TADV_COLS;
-        const int col = isL ? u0 + k : xr0 + (k - TADV_COLS);
-        // bit 31 marks a column outside the image (pixel bytes never set it): its e values are 0
-        const uint32_t v = (unsigned)col < (unsigned)W ? pixel(isL ? srcL : srcR, col) : 0x80000000u;
-        (isL ? sL : sR)[isL ? k : k - TADV_COLS] = v;
-    }
-    __syncthreads();
-    const int ncols = min(TADV_COLS, evolW - uc0);
-    uint32_t *const out = reinterpret_cast<uint32_t *>(evol + (((size_t)z * erows + by) * (size_t)evolW + uc0) * Se);
-    // rd = 4: dword `slot` of a column holds the disparities dlo + 4 slot + 0..3;  rd = 6 (asw_wave6_kernel.hip.h): a
-    // disparity group is an 8-byte slot, dword 2 g holds dlo + 6 g + 0..3 and dword 2 g + 1 holds dlo + 6 g + 4, 5
-    auto dword = [&](int c, int slot, uint32_t lp) {
-        uint32_t v = 0;
-        const int d0 = rd == 6 ? 6 * (slot >> 1) + 4 * (slot & 1) : 4 * slot, nv = rd == 6 && (slot & 1) ? 2 : 4;
-        if (!(lp >> 31) && d0 < Dc) {
-            // R[u - d] for d = dlo + d0 + q  ->  staged index c + (Dc - 1) - d0 - q
-            const uint32_t *const rp = sR + c + (Dc - 1) - d0;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const uint32_t rv = q < nv && d0 + q < Dc ? rp[-q] : 0x80000000u;
-                if (!(rv >> 31)) v |= min(__builtin_amdgcn_sad_u8(lp, rv, 0u), 40u) << (8 * q);
-            }
-        }
-        return v;
-    };
-    if ((P & 3) == 0) {
-        // rows of whole 16-byte blocks (the phase-shifted kernel's layout): a thread produces 16 disparities and one
-        // 16-byte store -- 1 KiB per wave and store instruction instead of 256 B
-        const int P4 = P >> 2;
-        uint4 *const out4 = reinterpret_cast<uint4 *>(out);
-        for (int k = threadIdx.x; k < ncols * P4; k += blockDim.x) {
-            const int c = k / P4, s4 = 4 * (k - c * P4);
-            const uint32_t lp = sL[c];
-            out4[k] = make_uint4(dword(c, s4, lp), dword(c, s4 + 1, lp), dword(c, s4 + 2, lp), dword(c, s4 + 3, lp));
-        }
-        return;
-    }
-    for (int k = threadIdx.x; k < ncols * P; k += blockDim.x) {
-        const int c = k / P, slot = k - c * P;
-        out[k] = dword(c, slot, sL[c]);
-    }
-}
-
-__global__ __launch_bounds__(256) void asw_tad_volume_kernel(const PixRec *__restrict__ recL, const PixRec *__restrict__ recR,
-                                                             unsigned char *__restrict__ evol, int W, int pad, int minD, int Dc,
-                                                             int Se, int erow0, int erows, int evolW, int rd = 4)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    asw_tad_tile<false>(recL, recR, evol, W, pad, minD, Dc, Se, erow0, erows, evolW, rd, 0, blockIdx.x, blockIdx.y, blockIdx.z, smem);
-}
-
-// K0 + K0e in ONE launch (round 5): the first `lab_blocks` workgroups convert the pixels of the rows [erow0, erow0 + erows) of both
-// images into records (bgr2lab_records_pair_kernel's job, same code), the others each build one tile of the volume from the
-// images' bytes.  The two jobs do not depend on each other, so a small-frame call is two dependent launches instead of three
-// (a launch-to-launch dependency costs more than either kernel at Tsukuba size).  bgrL / bgrR: the sub-image's row 0.
-struct AswPrepassArgs {
-    const uint8_t *bgrL, *bgrR;
-    PixRec *recL, *recR;
-    unsigned char *evol;
-    long long npix_total;            // pixels of the whole sub-image (bounds of the 4-byte pixel reads)
-    int W, pad, minD, Dc, Se, erow0, erows, evolW, rd;
-    int lab_blocks, ex, ey;          // grid: lab_blocks + ex * ey * ez workgroups
-};
-__global__ __launch_bounds__(256) void asw_prepass_kernel(const AswPrepassArgs P)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    if ((int)blockIdx.x < P.lab_blocks) {
-        SSAMD_LAB_TABLES_IN_LDS(T)
-        const long long np = (long long)P.erows * P.W, first = (long long)P.erow0 * P.W;
-        const uint8_t *const bl = P.bgrL + 3 * first, *const br = P.bgrR + 3 * first;
-        PixRec *const rl = P.recL + first, *const rr = P.recR + first;
-        typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
-        for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < 2 * np; q += (long long)P.lab_blocks * blockDim.x) {
-            const bool right = q >= np;
-            const long long p = right ? q - np : q;
-            const uint8_t *const bgr = right ? br : bl;
-            uint32_t B, G, R;
-            if (p + 1 < np) {
-                const uint32_t v = *reinterpret_cast<const u32_unaligned *>(bgr + 3 * p);
-                B = v & 0xff; G = (v >> 8) & 0xff; R = (v >> 16) & 0xff;
-            } else {
-                B = bgr[3 * p]; G = bgr[3 * p + 1]; R = bgr[3 * p + 2];
-            }
-            PixRec o;
-            bgr_to_lab(B, G, R, o.L, o.a, o.b, T);
-            o.bgrx = B | (G << 8) | (R << 16);
-            (right ? rr : rl)[p] = o;
-        }
-        return;
-    }
-    const int b = (int)blockIdx.x - P.lab_blocks, bx = b % P.ex, by = (b / P.ex) % P.ey, bz = b / (P.ex * P.ey);
-    asw_tad_tile<true>(P.bgrL, P.bgrR, P.evol, P.W, P.pad, P.minD, P.Dc, P.Se, P.erow0, P.erows, P.evolW, P.rd, P.npix_total, bx, by, bz, smem);
-}
-
-#endif  // SSAMD_KERNEL_TU
 
 // (A 6-column register tile -- 48 accumulators, 128 VGPRs, FOUR waves per SIMD in 1024-thread groups, right weights
 // read as 8-byte pairs -- was built and measured in round 2: bit-identical maps, 43.6 ms against 38.2 ms for this
@@ -184,31 +48,29 @@ __global__ __launch_bounds__(256) void asw_prepass_kernel(const AswPrepassArgs P
 // compile-time constants for the launch geometries of the headline configurations (0: read from the geometry at run
 // time).  The eight steps of a trip then address their operands with immediate offsets from one pointer per array,
 // advanced once per trip: 3 address instructions per 8 steps instead of 24 (107 -> 104.4 VALU instructions per step).
-// CG (round 6): the static instantiation takes the WHOLE tile geometry and the window from compile-time constants (see AswPipeTile);
-// false = strides only (rounds 3-5).  Both are built so that they can be compared in one process (SSAMD_ASW_STATIC=2 / 1).
+// (Round 6 also built instantiations with the WHOLE tile geometry and the window as constants: 1.7 ... 3.9 % slower,
+// profiles/r06_static_geometry_ab.txt; code removed.)
 // AswArgs must stay the kernel's ONLY parameter: the item loop reads it at offset 0 of the kernel-argument segment
 // (__builtin_amdgcn_kernarg_segment_ptr, see the loop at the end of the body).
-template <bool WITH_COSTS, int SLC = 0, int SRC = 0, int SEC = 0, bool CG = false>
+template <bool WITH_COSTS, int SLC = 0, int SRC = 0, int SEC = 0>
 __global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(const AswArgs A0)
 {
     constexpr bool STATIC = SLC > 0;
-    static_assert(!CG || STATIC, "compile-time geometry belongs to a static tile");
     constexpr int RX = ASW_RX;
     constexpr int NWR = asw_nwr(RX);
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    // static instantiations: the whole tile geometry and the window are compile-time constants (the launcher checked A.g against
-    // them: asw_pipe_geom_matches); the generic instantiation reads them from the arguments
-    constexpr AswGeom SG = asw_pipe_geom_constexpr(AswPipeTile<SLC, SRC, SEC>::id);
-    static_assert(!STATIC || (SG.SL == SLC && SG.SR == SRC && SG.Se == SEC), "the strides name the tile");
+    // a static stride triple is one the plain-row layout (asw_layout_e) produces: whole 8-column and 4-disparity groups, e rows of 16-byte blocks
+    static_assert(!STATIC || (SLC % 8 == 0 && (SRC - SLC) % 4 == 0 && SEC == 16 * (((SRC - SLC) / 4 + 3) / 4)),
+                  "the strides name a tile of the plain-row layout");
     // Persistent form (A.pq != nullptr, see the loop behind this lambda): the ticket of the workgroup's NEXT item, drawn from queue
     // pq_q under the current item and left in a dword of LDS the kernel has no other use for (AswGeom::off_prox)
-    uint32_t *const pq_next = reinterpret_cast<uint32_t *>(smem + (CG ? SG : A0.g).off_prox);
+    uint32_t *const pq_next = reinterpret_cast<uint32_t *>(smem + A0.g.off_prox);
     int pq_q = 0;
     // One work item: the tile (ibx, iby, ibz) of a grid of inx tiles per row -- blockIdx and gridDim.x of the plain launch.  A `return`
     // in here (and in asw_epilogue.inc) ends the item, not the kernel.  A: the kernel's arguments as the item reads them (see the loop).
     auto run_item = [&](const AswArgs &A, const int ibx, const int iby, const int ibz, const int inx) __attribute__((always_inline)) {
     const bool persist = A.pq != nullptr;
-    const AswGeom &g = CG ? SG : A.g;
+    const AswGeom &g = A.g;
     float *const wL = reinterpret_cast<float *>(smem + g.off_wL);
     float *const wR = reinterpret_cast<float *>(smem + g.off_wR);
     unsigned char *const eT0 = reinterpret_cast<unsigned char *>(smem + g.off_e);
@@ -221,7 +83,7 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(
     float4 *const cenLab = reinterpret_cast<float4 *>(smem + g.off_cen);
 
     const int tid = threadIdx.x, nthr = blockDim.x;
-    const int W = A.W, win = CG ? AswPipeTile<SLC, SRC, SEC>::id.win : A.win, p = CG ? AswPipeTile<SLC, SRC, SEC>::id.win / 2 : A.pad;
+    const int W = A.W, win = A.win, p = A.pad;
     const int Tx = g.Tx, Dc = g.Dc, nL = g.nL, nR = g.nR, nRc = g.nRc, SR = g.SR, Se = g.Se;
     const int JC = g.JC, NC = g.NC;
     // (the row stride as 64 bits, made here as a scalar pair: extended where a lane loop first needs it, inside the item loop the
@@ -352,9 +214,8 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(
         int tidw = threadIdx.x;
         asm volatile("" : "+v"(tidw));
         const int wave = __builtin_amdgcn_readfirstlane(tidw >> 6), lane = tidw & 63;
-        // (Tx = SL and nRc = SR - 1 in the plain-row layout, asw_layout_e: the static strides name them and the thread count)
-        constexpr int NTHR = STATIC ? asw_cx_round_up((SLC / ASW_RX) * ((SRC - SLC) / ASW_RD), 64) : 0;
-        static_assert(!STATIC || (SG.Tx == SLC && SG.nRc == SRC - 1 && SG.threads == NTHR), "the strides name the centres and the threads");
+        // (Tx == SL and nRc == SR - 1 are identities of the plain-row layout in asw_layout_e: the strides name the centres and the threads)
+        constexpr int NTHR = STATIC ? round_up((SLC / ASW_RX) * ((SRC - SLC) / ASW_RD), 64) : 0;
         const int TxB = STATIC ? SLC : Tx, nRcB = STATIC ? SRC - 1 : nRc, nw = (STATIC ? NTHR : nthr) >> 6;
         const int nLw = (TxB + 63) >> 6, ncw = nLw + ((nRcB + 63) >> 6);
         const float4 *const labLc = labL + (i & 1) * nL, *const labRc = labR + (i & 1) * nR;
@@ -495,7 +356,7 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(
         const unsigned char *const eT = eT0 + (i & 1) * g.e_bytes;
         AswRow ew[RX];
 
-#pragma nounroll                      // (NC is a compile-time 2 in the static instantiations: two copies of the tap loop cost VGPRs -> scratch)
+#pragma nounroll                      // (a tap loop per chunk costs VGPRs -> scratch: seen when round 6's whole-geometry form made NC a compile-time 2)
         for (int c = 0; c < NC; ++c) {
             __syncthreads();       // buffers of chunk (i, c) complete; every wave is done with chunk (i, c) - 1
             const int jc = c * JC, jend = chunk_end(c);

@@ -4,14 +4,11 @@
 // per-translation-unit option; the other kernel families lose with this one.
 // Also with -mllvm -disable-machine-licm (round 8): the kernel body is a loop over work items, and the thread-constant values the
 // machine-level hoisting lifts in front of that loop stay live through the tap loop (168 VGPRs: they went to scratch).
-#define SSAMD_KERNEL_TU 1
 #include <hip/hip_runtime.h>
 #include "asw_pipe_kernel.hip.h"
 
 namespace ssamd {
 #define SSAMD_PIPE_INSTANCE(C, SL, SR, SE) template __global__ void asw_aggregate_pipe_kernel<C, SL, SR, SE>(const AswArgs);
-#define SSAMD_PIPE_INSTANCE_CG(C, SL, SR, SE) template __global__ void asw_aggregate_pipe_kernel<C, SL, SR, SE, true>(const AswArgs);
 #include "asw_instances.inc"
-#undef SSAMD_PIPE_INSTANCE_CG
 #undef SSAMD_PIPE_INSTANCE
 }  // namespace ssamd

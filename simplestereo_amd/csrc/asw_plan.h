@@ -1,6 +1,7 @@
 // Launch planner of the ASW kernels: tile layouts in LDS, the cost model that picks a tile and a kernel form, the wave kernel's
 // strip.  Pure integer / double arithmetic: a function of its arguments (shape, window, PlanOptions) -- no HIP call, no global,
-// no tune(): the options come in with the caller.  The per-shape caches and the autotuner live with the operators (ssamd_api.hip), the only file that includes this.
+// no tune(): the options come in with the caller.  The per-shape caches and the autotuner live with the operators (ssamd_api.hip), the only file that includes this
+// (behind asw_shared.hip.h and asw_wave_kernel.hip.h: AswGeom, AswWaveGeom, the register-tile constants and round_up are theirs).
 #pragma once
 
 enum PlanResult { PLAN_OK = 0, PLAN_FORCED_UNUSABLE, PLAN_NO_FIT };     // (the operators turn these into error codes and messages)
@@ -10,8 +11,6 @@ struct PlanOptions {
     const Tuning &t;
     bool no_volume;           // the call cannot have the TAD volume: a phase-shifted tile must fit LDS with its staged colour bytes
 };
-
-inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 // ------------------------------------------------------------ ASW geometry
 bool asw_layout_e(AswGeom &g, const PlanOptions &po, int win, int XG, int DG, size_t limit, int JC, int Rx, bool e2, bool odd_pitch = false,

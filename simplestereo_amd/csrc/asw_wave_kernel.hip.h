@@ -20,7 +20,7 @@
 // e tiles come from the TAD volume of asw_tad_volume_kernel (LDS-DMA, one image row at a time).
 // Used when the whole range fits one chunk of at most 16 disparity groups (nD <= 64 since round 3; 48 in round 2).
 #pragma once
-#include "asw_kernels.hip.h"
+#include "asw_shared.hip.h"
 #include <type_traits>
 
 namespace ssamd {

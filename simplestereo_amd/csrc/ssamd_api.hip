@@ -19,19 +19,20 @@
 #include <vector>
 
 #include "../../include/ssamd.h"
+#include "asw_shared.hip.h"
 #include "asw_kernels.hip.h"
 #include "asw_pipe_kernel.hip.h"
 #include "asw_wave_kernel.hip.h"
 #include "asw_wave6_kernel.hip.h"
 #include "asw_alt_kernels.hip.h"
+#include "asw_prepass_kernels.hip.h"
+#include "asw_finalize_kernels.hip.h"
 // the phase-shifted and the six-per-lane kernels are instantiated in translation units of their own (asw_pipe_tu.hip, asw_wave6_tu.hip)
 namespace ssamd {
 #define SSAMD_PIPE_INSTANCE(C, SL, SR, SE) extern template __global__ void asw_aggregate_pipe_kernel<C, SL, SR, SE>(const AswArgs);
-#define SSAMD_PIPE_INSTANCE_CG(C, SL, SR, SE) extern template __global__ void asw_aggregate_pipe_kernel<C, SL, SR, SE, true>(const AswArgs);
 #define SSAMD_WAVE6_INSTANCE(C, K, CREG) extern template __global__ void asw_aggregate_wave6_kernel<C, K, CREG>(const AswWaveArgs);
 #include "asw_instances.inc"
 #undef SSAMD_PIPE_INSTANCE
-#undef SSAMD_PIPE_INSTANCE_CG
 #undef SSAMD_WAVE6_INSTANCE
 }  // namespace ssamd
 #include "gsw_kernels.hip.h"
@@ -211,7 +212,6 @@ struct Ctx {
     long long tail_splits = 0;          // phase-shifted launches whose last partial round of workgroups ran as half-width tiles
     long long exact_calls = 0;          // ASW calls that ran the fp64 tie-break pass
     long long persist_launches = 0;     // phase-shifted launches in the persistent form
-    long long static_tile_mismatch = 0; // pipe launches whose strides named a static tile that the full geometry did not match
     Profile prof;
 };
 
@@ -663,13 +663,11 @@ int launch_finalize(Ctx &c, int slot, bool lrcheck, int b0, int nb, int W, int16
 // (the list of what the other two translation units compile): what is selected here and what is compiled there cannot disagree
 using AswKernel = void (*)(const AswArgs);
 using AswWaveKernel = void (*)(const AswWaveArgs);
-struct AswPipeVariant { bool costs; int SL, SR, Se; bool cg; AswPipeTileId tile; AswKernel kernel; };
+struct AswPipeVariant { bool costs; int SL, SR, Se; AswKernel kernel; };
 const AswPipeVariant kPipeVariants[] = {
-#define SSAMD_PIPE_INSTANCE(C, SL, SR, SE) {C, SL, SR, SE, false, AswPipeTile<SL, SR, SE>::id, asw_aggregate_pipe_kernel<C, SL, SR, SE>},
-#define SSAMD_PIPE_INSTANCE_CG(C, SL, SR, SE) {C, SL, SR, SE, true, AswPipeTile<SL, SR, SE>::id, asw_aggregate_pipe_kernel<C, SL, SR, SE, true>},
+#define SSAMD_PIPE_INSTANCE(C, SL, SR, SE) {C, SL, SR, SE, asw_aggregate_pipe_kernel<C, SL, SR, SE>},
 #include "asw_instances.inc"
 #undef SSAMD_PIPE_INSTANCE
-#undef SSAMD_PIPE_INSTANCE_CG
 };
 // Wave kernels: RD disparities per lane (6: asw_instances.inc; 4: instantiated here), RX columns, and the build rounds known at
 // compile time (straight-line build) for the common combinations; KM > 0: merged build of KM rounds, else KL + KR separate rounds
@@ -694,20 +692,13 @@ const AswWaveVariant kWaveVariants[] = {
 // Strides known at compile time for the tiles of the headline configurations (immediate offsets in the
 // tap steps): 120 x 196 (1080p / D 0..192) and 88 x 260 (4096 x 2160 / D 0..256), 216 x 68 (D 0..64)
 // (with the cost / cost-image dump too: exact=True on the headline tiles ran the run-time-stride form, + 0.9 ms at 1080p / 193)
-// SSAMD_ASW_STATIC=2 (round 6 experiment): instantiations that take the WHOLE tile geometry and the window from compile-time
-// constants -- chosen only when the planned geometry equals the constexpr restatement field by field
-AswKernel asw_pick_pipe_kernel(Ctx &c, const AswGeom &g, int win, bool costs, int asw_static)
+AswKernel asw_pick_pipe_kernel(const AswGeom &g, bool costs, int asw_static)
 {
     AswKernel pk = nullptr;
     for (const AswPipeVariant &v : kPipeVariants) {
-        if (v.cg || v.costs != costs) continue;
+        if (v.costs != costs) continue;
         if (v.SL == 0 && !pk) pk = v.kernel;                                  // (the generic instantiation, unless a static one matched)
         if (asw_static != 0 && v.SL == g.SL && v.SR == g.SR && v.Se == g.Se) pk = v.kernel;
-    }
-    if (asw_static == 2 && !costs) {
-        for (const AswPipeVariant &v : kPipeVariants)
-            if (v.cg && !v.costs && win == v.tile.win && asw_pipe_geom_matches(g, asw_pipe_geom_constexpr(v.tile))) return v.kernel;
-        ++c.static_tile_mismatch;       // (counted: ssamd_counter "static_tile_mismatch")
     }
     return pk;
 }
@@ -954,7 +945,7 @@ int asw_launch_pipe(AswRun &r, const AswArgs &a, const dim3 &grid)
 {
     Ctx &c = r.c;
     const AswGeom &g = a.g;
-    const AswKernel pk = asw_pick_pipe_kernel(c, g, r.win, r.d_costs != nullptr, r.t.asw_static);
+    const AswKernel pk = asw_pick_pipe_kernel(g, r.d_costs != nullptr, r.t.asw_static);
     const int pipe_lds = a.evol ? g.lds_bytes_evol : g.lds_bytes;          // (no staged colour bytes when the e tiles come from the volume)
     if (pipe_lds > 160 * 1024) return fail(SSAMD_ELIMIT, "this tile needs the TAD volume (LDS %d bytes without it)", pipe_lds);
     if (int grc = grant_dyn_lds(c, (const void *)pk, pipe_lds)) return grc;
@@ -1017,7 +1008,7 @@ int asw_launch_pipe(AswRun &r, const AswArgs &a, const dim3 &grid)
         AswArgs t = a;
         t.g = tail_g;
         t.yb0 = rows_main;              // (workgroup rows continue; outputs are addressed by image row, so the buffers stay put)
-        const AswKernel tk = asw_pick_pipe_kernel(c, tail_g, r.win, r.d_costs != nullptr, 0);
+        const AswKernel tk = asw_pick_pipe_kernel(tail_g, r.d_costs != nullptr, 0);
         const int tail_lds = a.evol ? tail_g.lds_bytes_evol : tail_g.lds_bytes;
         if (int grc = grant_dyn_lds(c, (const void *)tk, tail_lds)) return grc;
         hipLaunchKernelGGL(tk, dim3((r.W + tail_g.Tx - 1) / tail_g.Tx, r.grows - rows_main, tail_g.nchunks), dim3(tail_g.threads),
@@ -1560,7 +1551,6 @@ int ssamd_counter(int device, const char *name, long long *value)
     else if (n == "evol_bytes") *value = (long long)c->evol.cap;
     else if (n == "tail_splits") *value = c->tail_splits;
     else if (n == "exact_calls") *value = c->exact_calls;
-    else if (n == "static_tile_mismatch") *value = c->static_tile_mismatch;
     else if (n == "pipe_persist_launches") *value = c->persist_launches;
     else if (n == "pipe_persist_items") {
         // tiles finished by persistent phase-shifted launches on this device so far (counted on the device, once per finished item)

@@ -16,7 +16,7 @@
     X("SSAMD_ASW_WAVE_WG", wave_wg, int, 0, std::max(1, std::min(4, atoi(v))), x != 0)   /* 0 unset (one wave per workgroup), 1..4 */ \
     X("SSAMD_ASW_WAVE_UNROLL", wave_unroll, int, 1, atoi(v), false)   /* 0: counted build loop */ \
     X("SSAMD_ASW_WAVE_MERGE", wave_merge, int, 1, atoi(v), x != 1)   /* 0: left and right centres of a strip in separate build rounds (round-2 form) */ \
-    X("SSAMD_ASW_STATIC", asw_static, int, 1, atoi(v), x != 1)   /* 0: the phase-shifted kernel always reads its strides from the geometry (round-2 form) */ \
+    X("SSAMD_ASW_STATIC", asw_static, int, 1, atoi(v), x != 1)   /* 0: the phase-shifted kernel always reads its strides from the geometry (round-2 form); anything else: stride constants where an instantiation has the tile's */ \
     X("SSAMD_ASW_EVOL_MAX_MB", evol_max_mb, int, 0, std::max(0, atoi(v)), x != 0)   /* 0 unset; else a cap of the TAD volume in MiB (tests of the paths taken when memory is short) */ \
     X("SSAMD_ASW_WAVE_RD", wave_rd, int, 0, atoi(v), x != 0)   /* 0: the host decides; 4: never the six-disparities-per-lane form of the wave kernel */ \
     X("SSAMD_ASW_NO_E2", no_e2, bool, false, true, x) \

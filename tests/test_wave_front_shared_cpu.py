@@ -11,8 +11,7 @@ WAVE_HEADERS = ["asw_wave_kernel.hip.h", "asw_wave6_kernel.hip.h"]
 SHARED_ONLY = ["__builtin_amdgcn_global_load_lds", "asw_weight_finish(", "__builtin_amdgcn_sqrtf", "tapoff["]
 # names a preprocessor conditional may test: the ones the build itself defines (simplestereo_amd/build.py, the translation units,
 # the compiler).  A compile-time variant of a kernel is a source tree of its own (tools/ab_tree.py), not an #ifdef.
-CONDITIONAL_NAMES = {"SSAMD_KERNEL_TU", "SSAMD_PIPE_INSTANCE", "SSAMD_PIPE_INSTANCE_CG", "SSAMD_WAVE6_INSTANCE", "GM_HOST_TABLES",
-                     "__HIPCC__", "__HIP_DEVICE_COMPILE__"}
+CONDITIONAL_NAMES = {"SSAMD_PIPE_INSTANCE", "SSAMD_WAVE6_INSTANCE", "GM_HOST_TABLES", "__HIPCC__", "__HIP_DEVICE_COMPILE__"}
 
 
 def _code(name):

@@ -19,7 +19,7 @@ cases = {"G6c": (make_pair(64, 96, 24, 5)[:2], dict(winSize=9, maxDisparity=24, 
 
 
 def key_of(c):
-    """asw_cost_key's image of a float32 cost (csrc/asw_kernels.hip.h) -- from the dumped cost itself, so the low side only"""
+    """asw_cost_key's image of a float32 cost (csrc/asw_shared.hip.h) -- from the dumped cost itself, so the low side only"""
     return np.float32(c).view(np.uint32)
 
 

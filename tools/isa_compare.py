@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
 """Is the device code of the working tree the device code of another revision?  (build container: CPU only)
 
-    python tools/isa_compare.py [REV]          # REV defaults to HEAD~1
+    python tools/isa_compare.py [--map OLD=NEW]... [REV]          # REV defaults to HEAD~1
 
 Exports REV's simplestereo_amd/csrc and include with `git archive`, compiles the translation units of
 simplestereo_amd/build.py (its flags, its per-unit -mllvm options) of both trees to gfx950 assembly, and compares the
 listings kernel by kernel: comments, blank lines and assembler directives are dropped, labels, instructions and each
-kernel's descriptor (.amdhsa_*: registers, LDS, scratch) are kept.  Prints one table row per unit and the names of the
-kernels that differ or exist on one side only; exits 1 if there are any.
+kernel's descriptor (.amdhsa_*: registers, LDS, scratch) are kept.  Block labels carry the function's index in its unit
+(.LBB<i>_<j>): the index is dropped, and so is the kernel's own entry label, so removing or renaming a kernel does not make
+the others differ.  --map OLD=NEW (repeatable) replaces the substring OLD by NEW in REV's symbols before the kernels are
+paired: a dropped template parameter changes the mangled names.  Prints one table row per unit and the names of the kernels
+that differ or exist on one side only; exits 1 if there are any.
 """
 import argparse
 import io
@@ -43,12 +46,18 @@ _TYPE = re.compile(r"\.type\s+(\S+),@function")
 _DESC = re.compile(r"\.amdhsa_kernel\s+(\S+)")
 
 
-def kernels(listing):
-    """{symbol: (instruction and label lines, descriptor lines)} of one listing."""
+_LBB = re.compile(r"\.LBB\d+_")
+
+
+def kernels(listing, renames=()):
+    """{symbol: (instruction and label lines, descriptor lines)} of one listing, its symbols renamed by (old, new) substrings."""
     out, name, desc = {}, None, None
     for raw in open(listing):
         line = raw.split(";", 1)[0].strip()
-        if not line:
+        for old, new in renames:
+            line = line.replace(old, new)
+        line = _LBB.sub(".LBB_", line)
+        if not line or line == "%s:" % name:
             continue
         m = _TYPE.match(line)
         if m:
@@ -73,7 +82,9 @@ def kernels(listing):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("rev", nargs="?", default="HEAD~1")
+    ap.add_argument("--map", action="append", default=[], metavar="OLD=NEW", help="substring replacement in REV's symbols")
     args = ap.parse_args()
+    renames = [tuple(m.split("=", 1)) for m in args.map]
     with tempfile.TemporaryDirectory(prefix="isa_compare_") as tmp:
         old_tree = os.path.join(tmp, "old")
         tar = subprocess.check_output(["git", "-C", ROOT, "archive", args.rev, CSRC, "include"])
@@ -87,7 +98,7 @@ def main():
         print(f"| unit | kernels {args.rev} / new | instructions {args.rev} / new | kernels differing |")
         print("|---|---|---|---|")
         for (src, lst_old, _), (_, lst_new, _) in zip(jobs[:n], jobs[n:]):
-            old, new = kernels(lst_old), kernels(lst_new)
+            old, new = kernels(lst_old, renames), kernels(lst_new)
             count = lambda ks: sum(1 for k in ks.values() for ln in k[0] if not ln.endswith(":"))
             diff = sorted(k for k in old.keys() | new.keys() if old.get(k) != new.get(k))
             print(f"| `{src}` | {len(old)} / {len(new)} | {count(old)} / {count(new)} | {len(diff)} |", flush=True)
