@@ -18,6 +18,8 @@
  *                           is the two calls of those lines, ssamd_ftp_phase with unwrap = 2 chains them)
  *   ssamd_ftp_phase    <->  the demodulation of StereoFTP.getCloud   simplestereo/active.py:675-737
  *                           (pure numpy in the reference: fft, band mask, ifft, angle; NOT the StereoFTP classes)
+ *   ssamd_ftp_cloud    <->  the triangulation of StereoFTP.getCloud   simplestereo/active.py:776-841
+ *                           (cv2.projectPoints / undistortPoints / perspectiveTransform in the reference)
  *   ssamd_*_device     same operators on buffers already resident in HBM (no
  *                      reference counterpart: the reference has no device).
  *
@@ -44,7 +46,7 @@
 extern "C" {
 #endif
 
-#define SSAMD_ABI_VERSION 8      /* 8: ssamd_np_unwrap / _device / _xy / _xy_device / _plan, ssamd_ftp_phase* unwrap = 2 and profile slot SSAMD_K_NPUNWRAP; 7: ssamd_ftp_phase / ssamd_ftp_phase_device / ssamd_ftp_band and profile slot SSAMD_K_FTP; 6: ssamd_iir_unwrap / ssamd_iir_unwrap_device and profile slot SSAMD_K_UNWRAP; 5:ssamd_asw_exact_device_rows2 / _rectified_device (round 6: near-ties selected inside the aggregation kernels); 4: ssamd_asw_exact* (round 5); 3: GSW autotuning; 2: ssamd_set_option (round 3) + the multi-device and verification entry points added in round 2 */
+#define SSAMD_ABI_VERSION 8      /* 8 also carries ssamd_ftp_cloud / ssamd_ftp_cloud_device (pure additions, billed to SSAMD_K_REPROJECT); 8: ssamd_np_unwrap / _device / _xy / _xy_device / _plan, ssamd_ftp_phase* unwrap = 2 and profile slot SSAMD_K_NPUNWRAP; 7: ssamd_ftp_phase / ssamd_ftp_phase_device / ssamd_ftp_band and profile slot SSAMD_K_FTP; 6: ssamd_iir_unwrap / ssamd_iir_unwrap_device and profile slot SSAMD_K_UNWRAP; 5:ssamd_asw_exact_device_rows2 / _rectified_device (round 6: near-ties selected inside the aggregation kernels); 4: ssamd_asw_exact* (round 5); 3: GSW autotuning; 2: ssamd_set_option (round 3) + the multi-device and verification entry points added in round 2 */
 
 #define SSAMD_OK 0
 #define SSAMD_EINVAL (-1)     /* bad argument (message tells which)            */
@@ -307,6 +309,37 @@ int ssamd_ftp_phase_device(const uint8_t *d_img_obj, int ch_obj, const uint8_t *
  * range, slo = 0, shi = -1 when none is kept. */
 int ssamd_ftp_band(int w, int h, const double *fmin, const double *fmax, int32_t *slo, int32_t *shi);
 
+/* ---- Fourier-transform profilometry: unwrapped phase -> point cloud ------------------------------------------------- */
+/* The triangulation of the reference's StereoFTP.getCloud (active.py:776-841, with the projector coordinates of
+ * _getProjectorMapping, :463-485): for the camera pixel (x, y) of the phase map, u = x + x0 + 0.5, v = y + y0 + 0.5 (pixel
+ * centres), projectPoints of (u, v, 1) onto the projector, the phase as a shift of the projector column, the row on the epipolar
+ * line, undistortPoints (5 iterations, P = K2), the two rectifying homographies, baseline / disparity and the common rotation
+ * undone.  One pointwise fp64 HIP kernel (csrc/ftp_cloud_kernels.hip.h), the operations of tests/_ftp_cloud_ref.py in its order,
+ * each rounded once; no bit-parity with cv2 is claimed.  A non-finite phase or a disparity of exactly 0 gives the non-finite
+ * values of the plain formulas at that pixel.
+ *   phase : fp64 [h][w], the unwrapped phase of the region of interest whose upper left camera pixel is (x0, y0)
+ *   k     : the fringe order (active.py:779-788); the kernel adds (k * 2) * pi to the phase (:791)
+ *   out   : fp64 [h][w][3]
+ *   geom  : HOST array of SSAMD_FTP_CLOUD_NGEOM doubles, consumed before the call returns; matrices row major:
+ *       [0..8]   M = z_plane * R * inv(K1), projectPoints' 3x3 "rvec", copied, not re-orthonormalised     active.py:479
+ *       [9..11]  T                                                                                         :480
+ *       [12..15] fx2, fy2, cx2, cy2 of K2 (the skew is ignored, as in OpenCV)                              :480
+ *       [16..27] distCoeffs2: k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4 (zeros where the model has fewer)          :481
+ *       [28..36] P = K2, all nine entries, of undistortPoints                                              :813
+ *       [37..38] epipole on the projector image, (K2 T / (K2 T)[2])[0..1]                                  :394-395
+ *       [39]     (2 pi) * fp, fp = 1 / period                                                              :799
+ *       [40..48] Rectify1   [49..57] Rectify2  (_lowLevelRectify, rectification.py:271-302)                 :390, :823, :830
+ *       [58..66] inv(commonR)                                                                              :398, :838
+ *       [67]     the baseline                                                                              :834
+ * SSAMD_EINVAL: a NULL pointer, a negative size or origin, h * w >= 2^31, a non-finite k or geom entry, buffers not 16-byte
+ * aligned (device form).  An empty map does nothing.
+ * ssamd_ftp_cloud: host buffers, synchronous (device as ssamd_iir_unwrap).  ssamd_ftp_cloud_device: device buffers, asynchronous
+ * on `stream`. */
+#define SSAMD_FTP_CLOUD_NGEOM 68
+int ssamd_ftp_cloud(const double *phase, int h, int w, int x0, int y0, const double *geom, double k, double *out, int device);
+int ssamd_ftp_cloud_device(const double *d_phase, int h, int w, int x0, int y0, const double *geom, double k, double *d_out,
+                           void *stream);
+
 /* ---- verification / measurement helpers ------------------------------------ */
 
 /* Raw left-referenced aggregated ASW costs, float32 [height][width][nD] with
@@ -359,7 +392,7 @@ int ssamd_debug_gsw_sqrt(int n, float *out);
 #define SSAMD_K_GSW_AGG 3    /* GSW weights + cost aggregation + WTA keys        */
 #define SSAMD_K_GSW_FIN 4    /* GSW LR check / occlusion fill                    */
 #define SSAMD_K_REMAP 5      /* rectification remap (bilinear)                    */
-#define SSAMD_K_REPROJECT 6  /* disparity -> 3-D points                           */
+#define SSAMD_K_REPROJECT 6  /* disparity -> 3-D points; FTP phase -> 3-D points (ftp_cloud_kernel) */
 #define SSAMD_K_ASW_ALT 7    /* alternate-rows mode: bounded search on the odd rows */
 #define SSAMD_K_ASW_EXACT 8  /* fp64 tie-break pass of ssamd_asw_exact* (fp64 Lab, filter, winners, eval, resolve, patch) */
 #define SSAMD_K_UNWRAP 9     /* phase unwrapping wavefront (iir_unwrap_kernel)                                     */

@@ -115,6 +115,10 @@ def lib():
     L.ssamd_ftp_phase.argtypes = [P, I, P, I, I, I, P, P, I, D, P, I]
     L.ssamd_ftp_phase_device.restype = I
     L.ssamd_ftp_phase_device.argtypes = [P, I, P, I, I, I, P, P, I, D, P, P]
+    L.ssamd_ftp_cloud.restype = I
+    L.ssamd_ftp_cloud.argtypes = [P, I, I, I, I, P, D, P, I]
+    L.ssamd_ftp_cloud_device.restype = I
+    L.ssamd_ftp_cloud_device.argtypes = [P, I, I, I, I, P, D, P, P]
     L.ssamd_ftp_band.restype = I
     L.ssamd_ftp_band.argtypes = [I, I, P, P, P, P]
     LL = ctypes.c_longlong
