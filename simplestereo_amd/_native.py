@@ -7,6 +7,8 @@ visible, the calls fail loudly.
 import ctypes
 import os
 
+import numpy as np
+
 from .build import LIB_PATH as _DEFAULT_LIB_PATH
 
 # experiments only (a library built from another source tree, tools/ab_tree.py): another build of the same library is loaded
@@ -21,10 +23,55 @@ ABI_VERSION = 8
 
 (K_LAB, K_ASW_AGG, K_ASW_FIN, K_GSW_AGG, K_GSW_FIN, K_REMAP, K_REPROJECT, K_ASW_ALT, K_ASW_EXACT, K_UNWRAP, K_FTP,
  K_NPUNWRAP, K_COUNT) = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12
+OK, EINVAL, ENODEVICE, EHIP, ENOMEM, ELIMIT = 0, -1, -2, -3, -4, -5
 
 _lib = None
-_u8p = ctypes.c_void_p
-_i16p = ctypes.c_void_p
+
+# Every function of include/ssamd.h once: argument types -> the entry points that take them.  i int, l long long, d double,
+# f float, p a buffer (host or device) or a stream, s const char *, I / L / D pointers to int (int32_t) / long long / double;
+# all return int but the two of _RETURN_STRING.  tests/test_native_signatures_cpu.py holds the table to the header.
+_ASW, _GSW = "iiiddi", "iiiifii"      # winSize, maxDisparity, minDisparity + gammaC, gammaP, consistent / gamma, fMax, iterations, bins
+_SIGNATURES = (
+    ("", "ssamd_abi_version ssamd_last_error ssamd_device_count ssamd_profile_reset"),
+    ("ppii" + _ASW + "pi", "ssamd_asw ssamd_asw_exact ssamd_asw_alternate"),
+    ("ppii" + _ASW + "pIi", "ssamd_asw_multi ssamd_asw_exact_multi ssamd_asw_alternate_multi"),
+    ("ppiiii" + _ASW + "pp", "ssamd_asw_device ssamd_asw_exact_device"),
+    ("ppiiiiii" + _ASW + "pp", "ssamd_asw_device_rows2 ssamd_asw_exact_device_rows2"),
+    ("ppiippppiii" + _ASW + "pp", "ssamd_asw_rectified_device ssamd_asw_exact_rectified_device"),
+    ("ppii" + _ASW + "pp", "ssamd_asw_alternate_device"),
+    ("ppiiiii" + _ASW + "pp", "ssamd_asw_alternate_rows_device"),
+    ("ppii" + _GSW + "pi", "ssamd_gsw"),
+    ("ppii" + _GSW + "pIi", "ssamd_gsw_multi"),
+    ("ppiiii" + _GSW + "pp", "ssamd_gsw_device"),
+    ("ppiiiiii" + _GSW + "pp", "ssamd_gsw_device_rows2"),
+    ("ppiippppiii" + _GSW + "pp", "ssamd_gsw_rectified_device"),
+    ("ppiiiiiddpi", "ssamd_asw_costs"),
+    ("ppiiiiiddppi", "ssamd_asw_argmins"),
+    ("piipi", "ssamd_bgr2lab"),
+    ("piippiiipp", "ssamd_remap_bgr_device"),
+    ("piiDpp", "ssamd_reproject_device"),
+    ("iipppp", "ssamd_ftp_band"),
+    ("lllI", "ssamd_np_unwrap_plan"),
+    ("ilppp", "ssamd_debug_exact_queue"),
+    ("iipp", "ssamd_debug_libm"),
+    ("ppiiiddipppp", "ssamd_debug_exact_costs"),
+    ("ip", "ssamd_debug_gsw_sqrt"),
+    ("i", "ssamd_profile_enable ssamd_kernel_name ssamd_autotune"),
+    ("DL", "ssamd_profile_read"),
+    ("iiiiiI", "ssamd_asw_geometry ssamd_asw_kernel_form ssamd_gsw_geometry"),
+    ("ss", "ssamd_set_option"),
+    ("isL", "ssamd_counter"),
+) + tuple((args + last, name + suffix) for args, name in (       # NAME(..., int device) and NAME_device(..., void *stream)
+    ("piiidp", "ssamd_iir_unwrap"),
+    ("plllddp", "ssamd_np_unwrap"),
+    ("piiip", "ssamd_np_unwrap_xy"),
+    ("pipiiippidp", "ssamd_ftp_phase"),
+    ("piiiipdp", "ssamd_ftp_cloud"),
+) for last, suffix in (("i", ""), ("p", "_device")))
+_RETURN_STRING = ("ssamd_last_error", "ssamd_kernel_name")
+_CTYPES = {"i": ctypes.c_int, "l": ctypes.c_longlong, "d": ctypes.c_double, "f": ctypes.c_float, "p": ctypes.c_void_p,
+           "s": ctypes.c_char_p, "I": ctypes.POINTER(ctypes.c_int), "L": ctypes.POINTER(ctypes.c_longlong),
+           "D": ctypes.POINTER(ctypes.c_double)}
 
 
 class NativeError(RuntimeError):
@@ -59,112 +106,67 @@ def lib():
     if L.ssamd_abi_version() != ABI_VERSION:
         raise ImportError("%s has ABI version %d, this package needs %d: rebuild it with `python -m simplestereo_amd.build`"
                           % (LIB_PATH, L.ssamd_abi_version(), ABI_VERSION))
-    I, D, F, P = ctypes.c_int, ctypes.c_double, ctypes.c_float, ctypes.c_void_p
-    L.ssamd_abi_version.restype = I
-    L.ssamd_last_error.restype = ctypes.c_char_p
-    L.ssamd_device_count.restype = I
-    L.ssamd_asw.restype = I
-    L.ssamd_asw.argtypes = [P, P, I, I, I, I, I, D, D, I, P, I]
-    L.ssamd_gsw.restype = I
-    L.ssamd_gsw.argtypes = [P, P, I, I, I, I, I, I, F, I, I, P, I]
-    L.ssamd_asw_multi.restype = I
-    L.ssamd_asw_multi.argtypes = [P, P, I, I, I, I, I, D, D, I, P, ctypes.POINTER(I), I]
-    L.ssamd_gsw_multi.restype = I
-    L.ssamd_gsw_multi.argtypes = [P, P, I, I, I, I, I, I, F, I, I, P, ctypes.POINTER(I), I]
-    L.ssamd_asw_device.restype = I
-    L.ssamd_asw_device.argtypes = [P, P, I, I, I, I, I, I, I, D, D, I, P, P]
-    L.ssamd_gsw_device.restype = I
-    L.ssamd_gsw_device.argtypes = [P, P, I, I, I, I, I, I, I, I, F, I, I, P, P]
-    L.ssamd_asw_device_rows2.restype = I
-    L.ssamd_asw_device_rows2.argtypes = [P, P, I, I, I, I, I, I, I, I, I, D, D, I, P, P]
-    L.ssamd_asw_exact.restype = I
-    L.ssamd_asw_exact.argtypes = [P, P, I, I, I, I, I, D, D, I, P, I]
-    L.ssamd_asw_exact_multi.restype = I
-    L.ssamd_asw_exact_multi.argtypes = [P, P, I, I, I, I, I, D, D, I, P, ctypes.POINTER(I), I]
-    L.ssamd_asw_exact_device.restype = I
-    L.ssamd_asw_exact_device.argtypes = [P, P, I, I, I, I, I, I, I, D, D, I, P, P]
-    L.ssamd_gsw_device_rows2.restype = I
-    L.ssamd_gsw_device_rows2.argtypes = [P, P, I, I, I, I, I, I, I, I, I, I, F, I, I, P, P]
-    L.ssamd_asw_exact_device_rows2.restype = I
-    L.ssamd_asw_exact_device_rows2.argtypes = [P, P, I, I, I, I, I, I, I, I, I, D, D, I, P, P]
-    L.ssamd_asw_exact_rectified_device.restype = I
-    L.ssamd_asw_exact_rectified_device.argtypes = [P, P, I, I, P, P, P, P, I, I, I, I, I, I, D, D, I, P, P]
-    L.ssamd_asw_alternate.restype = I
-    L.ssamd_asw_alternate.argtypes = [P, P, I, I, I, I, I, D, D, I, P, I]
-    L.ssamd_asw_alternate_device.restype = I
-    L.ssamd_asw_alternate_device.argtypes = [P, P, I, I, I, I, I, D, D, I, P, P]
-    L.ssamd_asw_alternate_rows_device.restype = I
-    L.ssamd_asw_alternate_rows_device.argtypes = [P, P, I, I, I, I, I, I, I, I, D, D, I, P, P]
-    L.ssamd_asw_alternate_multi.restype = I
-    L.ssamd_asw_alternate_multi.argtypes = [P, P, I, I, I, I, I, D, D, I, P, ctypes.POINTER(I), I]
-    L.ssamd_asw_costs.restype = I
-    L.ssamd_asw_costs.argtypes = [P, P, I, I, I, I, I, D, D, P, I]
-    L.ssamd_asw_argmins.restype = I
-    L.ssamd_asw_argmins.argtypes = [P, P, I, I, I, I, I, D, D, P, P, I]
-    L.ssamd_bgr2lab.restype = I
-    L.ssamd_bgr2lab.argtypes = [P, I, I, P, I]
-    L.ssamd_remap_bgr_device.restype = I
-    L.ssamd_remap_bgr_device.argtypes = [P, I, I, P, P, I, I, I, P, P]
-    L.ssamd_reproject_device.restype = I
-    L.ssamd_reproject_device.argtypes = [P, I, I, ctypes.POINTER(D), P, P]
-    L.ssamd_iir_unwrap.restype = I
-    L.ssamd_iir_unwrap.argtypes = [P, I, I, I, D, P, I]
-    L.ssamd_iir_unwrap_device.restype = I
-    L.ssamd_iir_unwrap_device.argtypes = [P, I, I, I, D, P, P]
-    L.ssamd_ftp_phase.restype = I
-    L.ssamd_ftp_phase.argtypes = [P, I, P, I, I, I, P, P, I, D, P, I]
-    L.ssamd_ftp_phase_device.restype = I
-    L.ssamd_ftp_phase_device.argtypes = [P, I, P, I, I, I, P, P, I, D, P, P]
-    L.ssamd_ftp_cloud.restype = I
-    L.ssamd_ftp_cloud.argtypes = [P, I, I, I, I, P, D, P, I]
-    L.ssamd_ftp_cloud_device.restype = I
-    L.ssamd_ftp_cloud_device.argtypes = [P, I, I, I, I, P, D, P, P]
-    L.ssamd_ftp_band.restype = I
-    L.ssamd_ftp_band.argtypes = [I, I, P, P, P, P]
-    LL = ctypes.c_longlong
-    L.ssamd_np_unwrap.restype = I
-    L.ssamd_np_unwrap.argtypes = [P, LL, LL, LL, D, D, P, I]
-    L.ssamd_np_unwrap_device.restype = I
-    L.ssamd_np_unwrap_device.argtypes = [P, LL, LL, LL, D, D, P, P]
-    L.ssamd_np_unwrap_xy.restype = I
-    L.ssamd_np_unwrap_xy.argtypes = [P, I, I, I, P, I]
-    L.ssamd_np_unwrap_xy_device.restype = I
-    L.ssamd_np_unwrap_xy_device.argtypes = [P, I, I, I, P, P]
-    L.ssamd_np_unwrap_plan.restype = I
-    L.ssamd_np_unwrap_plan.argtypes = [LL, LL, LL, ctypes.POINTER(ctypes.c_int32)]
-    L.ssamd_debug_exact_queue.restype = I
-    L.ssamd_debug_exact_queue.argtypes = [I, ctypes.c_longlong, P, P, P]
-    L.ssamd_debug_libm.restype = I
-    L.ssamd_debug_libm.argtypes = [I, I, P, P]
-    L.ssamd_debug_exact_costs.restype = I
-    L.ssamd_debug_exact_costs.argtypes = [P, P, I, I, I, D, D, I, P, P, P, P]
-    L.ssamd_debug_gsw_sqrt.restype = I
-    L.ssamd_debug_gsw_sqrt.argtypes = [I, P]
-    L.ssamd_profile_enable.restype = I
-    L.ssamd_profile_enable.argtypes = [I]
-    L.ssamd_profile_reset.restype = I
-    L.ssamd_profile_read.restype = I
-    L.ssamd_profile_read.argtypes = [ctypes.POINTER(D), ctypes.POINTER(ctypes.c_longlong)]
-    L.ssamd_kernel_name.restype = ctypes.c_char_p
-    L.ssamd_kernel_name.argtypes = [I]
-    L.ssamd_autotune.restype = I
-    L.ssamd_autotune.argtypes = [I]
-    L.ssamd_asw_geometry.restype = I
-    L.ssamd_asw_geometry.argtypes = [I, I, I, I, I, ctypes.POINTER(I)]
-    L.ssamd_asw_kernel_form.restype = I
-    L.ssamd_asw_kernel_form.argtypes = [I, I, I, I, I, ctypes.POINTER(I)]
-    L.ssamd_gsw_geometry.restype = I
-    L.ssamd_gsw_geometry.argtypes = [I, I, I, I, I, ctypes.POINTER(I)]
-    L.ssamd_set_option.restype = I
-    L.ssamd_set_option.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
-    L.ssamd_asw_rectified_device.restype = I
-    L.ssamd_asw_rectified_device.argtypes = [P, P, I, I, P, P, P, P, I, I, I, I, I, I, D, D, I, P, P]
-    L.ssamd_gsw_rectified_device.restype = I
-    L.ssamd_gsw_rectified_device.argtypes = [P, P, I, I, P, P, P, P, I, I, I, I, I, I, I, F, I, I, P, P]
-    L.ssamd_counter.restype = I
-    L.ssamd_counter.argtypes = [I, ctypes.c_char_p, ctypes.POINTER(ctypes.c_longlong)]
+    for args, names in _SIGNATURES:
+        for name in names.split():
+            fn = getattr(L, name)
+            fn.restype = ctypes.c_char_p if name in _RETURN_STRING else ctypes.c_int
+            fn.argtypes = [_CTYPES[a] for a in args]
     _lib = L
     return L
+
+
+def check(rc, invalid=()):
+    """Raise for a negative return code: ``ValueError`` with the library's message for the codes in ``invalid`` (a bad argument
+    of the caller's, e.g. ``(EINVAL, ELIMIT)``), ``NativeError`` for every other."""
+    if rc != 0:
+        msg = lib().ssamd_last_error().decode("utf-8", "replace")
+        if rc in invalid:
+            raise ValueError(msg) from None
+        raise NativeError(rc, msg)
+
+
+def is_device_tensor(x):
+    return type(x).__module__.startswith("torch") and hasattr(x, "is_cuda") and bool(x.is_cuda)
+
+
+def c_double(v, strict=True):
+    """PyArg_ParseTuple 'd' / 'f': a float, an int (bool included) or anything with __float__ / __index__.  ``strict`` also
+    refuses strings and numbers beyond a double; without it anything float() accepts passes."""
+    if strict and isinstance(v, (str, bytes, bytearray)):
+        raise ValueError("Invalid input format!")
+    try:
+        return float(v)
+    except ((TypeError, ValueError, OverflowError) if strict else (TypeError, ValueError)):
+        raise ValueError("Invalid input format!") from None
+
+
+def call_on_stream(t, fn, *args, invalid=()):
+    """``fn(*args, stream)`` of a ``*_device`` entry point with the device of the tensor ``t`` current and ``stream`` that
+    device's current stream; return codes as in :func:`check`."""
+    import torch
+    with torch.cuda.device(t.device):
+        rc = fn(*args, ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream))
+        if rc:
+            check(rc, invalid)
+
+
+def run(name, sources, shape, args, invalid=()):
+    """The operator ``name`` on host arrays, or ``name + "_device"`` on device tensors (``sources``: all of one kind; made
+    contiguous): the float64 result of ``shape`` is allocated like them and returned as it is, without a native call, when an
+    extent is 0.  ``args(pointers of the sources ..., pointer of the result)`` gives every argument but the last, which is
+    the current device (-1) or the current stream."""
+    if is_device_tensor(sources[0]):
+        import torch
+        srcs = [s.contiguous() for s in sources]
+        out = torch.empty(shape, dtype=torch.float64, device=srcs[0].device)
+        if 0 not in shape:
+            call_on_stream(out, getattr(lib(), name + "_device"), *args(*[s.data_ptr() for s in srcs], out.data_ptr()), invalid=invalid)
+        return out
+    srcs = [np.ascontiguousarray(s) for s in sources]
+    out = np.empty(shape, dtype=np.float64)
+    if 0 not in shape:
+        check(getattr(lib(), name)(*args(*[s.ctypes.data for s in srcs], out.ctypes.data), -1), invalid)
+    return out
 
 
 def set_option(name, value):
@@ -204,11 +206,6 @@ class options:
         for k in self.kw:
             set_option(k, None)
         return False
-
-
-def check(rc):
-    if rc != 0:
-        raise NativeError(rc, lib().ssamd_last_error().decode("utf-8", "replace"))
 
 
 def profile_read():

@@ -28,6 +28,9 @@ import json
 
 import numpy as np
 
+from . import _native
+from ._native import is_device_tensor as _is_device_tensor
+
 __all__ = ["StereoRig", "RectifiedStereoRig"]
 
 # OpenCV interpolation flag values, so callers can pass cv2.INTER_* or these
@@ -208,10 +211,6 @@ def _fitting_matrix(K1, K2, H1, H2, dims1, dims2, dist1=None, dist2=None, destDi
     s = (s - 1) * (1 - alpha) + 1
     Kz = np.array([[s, 0, -s * left], [0, s, -s * top], [0, 0, 1]], dtype=np.float64)
     return Kz.dot(Fit)
-
-
-def _is_device_tensor(x):
-    return type(x).__module__.startswith("torch") and hasattr(x, "is_cuda") and bool(x.is_cuda)
 
 
 class StereoRig:
@@ -430,9 +429,7 @@ class RectifiedStereoRig(StereoRig):
         return cache[key]
 
     def _remap_device(self, img, which, interpolation):
-        import ctypes
         import torch
-        from . import _native
         if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
             raise ValueError("device rectification expects uint8 [H,W,3] tensors")
         if interpolation not in (INTER_NEAREST, INTER_LINEAR):
@@ -441,11 +438,8 @@ class RectifiedStereoRig(StereoRig):
         src = img.contiguous()
         h, w = (self.mapx1 if which == 1 else self.mapx2).shape
         out = torch.empty((h, w, 3), dtype=torch.uint8, device=img.device)
-        with torch.cuda.device(img.device):
-            stream = torch.cuda.current_stream(img.device).cuda_stream
-            _native.check(_native.lib().ssamd_remap_bgr_device(src.data_ptr(), int(src.shape[0]), int(src.shape[1]),
-                                                               dmx.data_ptr(), dmy.data_ptr(), h, w, int(interpolation),
-                                                               out.data_ptr(), ctypes.c_void_p(stream)))
+        _native.call_on_stream(img, _native.lib().ssamd_remap_bgr_device, src.data_ptr(), int(src.shape[0]), int(src.shape[1]),
+                               dmx.data_ptr(), dmy.data_ptr(), h, w, int(interpolation), out.data_ptr())
         return out
 
     def getQ(self):
@@ -488,7 +482,6 @@ class RectifiedStereoRig(StereoRig):
         """int16 disparity tensor on the GPU -> float32 [H,W,3] point tensor on the GPU (reproject_kernel)."""
         import ctypes
         import torch
-        from . import _native
         if disp.dtype != torch.int16 or disp.dim() != 2:
             raise ValueError("device reprojection expects an int16 [H,W] tensor")
         d = disp.contiguous()
@@ -497,9 +490,6 @@ class RectifiedStereoRig(StereoRig):
             d = d.clone()         # a view at an odd storage offset: the kernel reads four disparities per 8-byte load
         Q = np.ascontiguousarray(self.getQ(), dtype=np.float64)
         out = torch.empty((h, w, 3), dtype=torch.float32, device=d.device)
-        with torch.cuda.device(d.device):
-            stream = torch.cuda.current_stream(d.device).cuda_stream
-            _native.check(_native.lib().ssamd_reproject_device(d.data_ptr(), h, w,
-                                                               Q.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                                               out.data_ptr(), ctypes.c_void_p(stream)))
+        _native.call_on_stream(d, _native.lib().ssamd_reproject_device, d.data_ptr(), h, w,
+                               Q.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), out.data_ptr())
         return out

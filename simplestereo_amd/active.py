@@ -69,15 +69,13 @@ map; ``stripeCentralPeak`` not a finite number
 
 All of them are raised before any native call.  An image or a phase map with no rows or no columns gives an empty array.
 """
-import ctypes
 import numbers
 
 import numpy as np
 
 from . import _native
 from ._rigs import _dist_vector
-from .passive import _is_device_tensor
-from .unwrapping import _c_double
+from ._native import c_double as _c_double, is_device_tensor as _is_device_tensor
 
 __all__ = ["ftpPhase", "ftpCloud", "ftpFringeOrder", "ftpGeometry", "FtpGeometry", "MAX_WIDTH"]
 
@@ -130,10 +128,7 @@ def _band(fc, radius_factor, h):
     return np.ascontiguousarray(fmin), np.ascontiguousarray(fmax)
 
 
-def _raise_native(e):
-    if e.code in (-1, -5):          # SSAMD_EINVAL, SSAMD_ELIMIT
-        raise ValueError(e.message) from None
-    raise e
+_INVALID = (_native.EINVAL, _native.ELIMIT)
 
 
 def ftpPhase(imgObj, imgRef, fc, radius_factor=0.5, unwrap=None, tau=1):
@@ -190,29 +185,8 @@ def ftpPhase(imgObj, imgRef, fc, radius_factor=0.5, unwrap=None, tau=1):
     if w > MAX_WIDTH:
         raise ValueError("rows wider than %d columns are not supported (width %d)" % (MAX_WIDTH, w))
     uw = {None: 0, "iir": 1, "numpy": 2}[unwrap]
-    if dev:
-        import torch
-        out = torch.empty((h, w), dtype=torch.float64, device=obj.device)
-        if h == 0 or w == 0:
-            return out
-        with torch.cuda.device(obj.device):
-            stream = torch.cuda.current_stream(obj.device).cuda_stream
-            try:
-                _native.check(_native.lib().ssamd_ftp_phase_device(obj.data_ptr(), ch_obj, ref.data_ptr(), ch_ref, h, w,
-                                                                   fmin.ctypes.data, fmax.ctypes.data, uw, t, out.data_ptr(),
-                                                                   ctypes.c_void_p(stream)))
-            except _native.NativeError as e:
-                _raise_native(e)
-        return out
-    out = np.empty((h, w), dtype=np.float64)
-    if h == 0 or w == 0:
-        return out
-    try:
-        _native.check(_native.lib().ssamd_ftp_phase(obj.ctypes.data, ch_obj, ref.ctypes.data, ch_ref, h, w, fmin.ctypes.data,
-                                                    fmax.ctypes.data, uw, t, out.ctypes.data, -1))
-    except _native.NativeError as e:
-        _raise_native(e)
-    return out
+    return _native.run("ssamd_ftp_phase", (obj, ref), (h, w),
+                       lambda o, r, out: (o, ch_obj, r, ch_ref, h, w, fmin.ctypes.data, fmax.ctypes.data, uw, t, out), _INVALID)
 
 
 # ------------------------------------------------------------------------------------------------ phase -> point cloud
@@ -450,27 +424,7 @@ def ftpCloud(phaseUnwrapped, rig, z_plane=None, period=None, k=0, roi=None):
     phase, dev = _phase_map(phaseUnwrapped, G.roi)
     x0, y0, w, h = G.roi
     if dev:
-        import torch
-        out = torch.empty((h, w, 3), dtype=torch.float64, device=phase.device)
-        if h == 0 or w == 0:
-            return out
-        src = phase.contiguous()
-        if src.data_ptr() % 16:
-            src = src.clone()         # a view at an odd storage offset: the kernel reads two phases per 16-byte load
-        with torch.cuda.device(src.device):
-            stream = torch.cuda.current_stream(src.device).cuda_stream
-            try:
-                _native.check(_native.lib().ssamd_ftp_cloud_device(src.data_ptr(), h, w, x0, y0, G.geom.ctypes.data, order,
-                                                                   out.data_ptr(), ctypes.c_void_p(stream)))
-            except _native.NativeError as e:
-                _raise_native(e)
-        return out
-    out = np.empty((h, w, 3), dtype=np.float64)
-    if h == 0 or w == 0:
-        return out
-    src = np.ascontiguousarray(phase)
-    try:
-        _native.check(_native.lib().ssamd_ftp_cloud(src.ctypes.data, h, w, x0, y0, G.geom.ctypes.data, order, out.ctypes.data, -1))
-    except _native.NativeError as e:
-        _raise_native(e)
-    return out
+        phase = phase.contiguous()
+        if phase.data_ptr() % 16:
+            phase = phase.clone()     # a view at an odd storage offset: the kernel reads two phases per 16-byte load
+    return _native.run("ssamd_ftp_cloud", (phase,), (h, w, 3), lambda src, out: (src, h, w, x0, y0, G.geom.ctypes.data, order, out), _INVALID)

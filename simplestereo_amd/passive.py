@@ -44,15 +44,18 @@ reference as well (``_passive.cpp:372-374``).
 (reference ``passive.py:43-46``) and never implemented.
 """
 import ctypes
+import functools
 import operator
 
 import numpy as np
 
 from . import _native
+from ._native import is_device_tensor as _is_device_tensor
 
 __all__ = ["StereoASW", "StereoGSW", "set_autotune"]
 
 _INT_MIN, _INT_MAX = -2 ** 31, 2 ** 31 - 1
+_INVALID = (_native.EINVAL,)          # the return code that is a ValueError of the caller's
 
 
 def _c_int(v):
@@ -67,16 +70,7 @@ def _c_int(v):
     return i
 
 
-def _c_double(v):
-    """PyArg_ParseTuple 'd' / 'f': anything float() accepts."""
-    try:
-        return float(v)
-    except (TypeError, ValueError):
-        raise ValueError("Invalid input format!") from None
-
-
-def _is_device_tensor(x):
-    return type(x).__module__.startswith("torch") and hasattr(x, "is_cuda") and bool(x.is_cuda)
+_c_double = functools.partial(_native.c_double, strict=False)      # PyArg_ParseTuple 'd' / 'f': anything float() accepts
 
 
 def _check_pair(img1, img2):
@@ -134,13 +128,118 @@ def set_autotune(on=True):
     return None if before < 0 else bool(before)
 
 
-def _raise_native(e):
-    if e.code == -1:
-        raise ValueError(e.message) from None
-    raise e
+class _Matcher:
+    """``compute`` and its two device routes, once for both matchers.  A matcher gives ``_params()`` -- the native arguments from
+    ``winSize, maxDisparity, minDisparity`` up to the output pointer -- and ``_entry(lib, route, exact, row_parity)``: the native
+    function of a route (``"host"``, ``"multi"``, ``"device"``, ``"rows2"`` or ``"rectified"``, the suffixes of ``_ROUTES``) and
+    the arguments it takes ahead of ``winSize``."""
+    _ROUTES = {"host": "", "multi": "_multi", "device": "_device", "rows2": "_device_rows2", "rectified": "_rectified_device"}
+
+    def _alternate(self, cons):
+        return False
+
+    def _exact(self):
+        return False
+
+    def compute(self, img1, img2, devices=None, rectify=None, interpolation=1):
+        """
+        Disparity map of a rectified BGR pair.
+
+        img1, img2: left and right image, ``numpy.uint8`` arrays ``[H, W, 3]`` in OpenCV channel
+        order (or two device tensors, see the module docstring).  Returns a new ``numpy.int16``
+        array ``[H, W]`` of left-referenced disparities.  ``devices`` (extension, host arrays only):
+        list of GPU indices that share the frame as row strips.
+
+        ``rectify`` (extension, device tensors only): a ``RectifiedStereoRig`` whose maps are computed -- ``img1`` / ``img2``
+        are then the RAW frames, and ``rig.rectifyImages(img1, img2, interpolation)`` followed by ``compute`` (the reference's
+        pipeline, examples/009) runs as one call in which rectification and the matcher's pixel records (ASW: the Lab
+        conversion) are a single launch and the rectified frames never exist in HBM.  Same map, bit for bit, as the two calls.
+        """
+        if rectify is not None:
+            if not (_is_device_tensor(img1) and _is_device_tensor(img2)) or devices is not None:
+                raise ValueError("rectify=rig applies to two device tensors (raw frames resident in HBM)")
+            if tuple(img1.shape) != tuple(img2.shape):
+                # cameras of different resolutions (res1 != res2, which rectifyImages supports): the fused launch takes one
+                # source size for both frames, so such rigs go through the two calls it otherwise replaces -- same map
+                return self.compute(*rectify.rectifyImages(img1, img2, interpolation))
+            return self._compute_rectified_device(rectify, img1, img2, interpolation)
+        if _is_device_tensor(img1) and _is_device_tensor(img2):
+            if devices is not None:
+                raise ValueError("devices=[...] applies to host arrays; device tensors are matched where they live")
+            return self._match_device(img1, img2, 0, None, 0, None, None)
+        lib = _native.lib()
+        if not isinstance(img1, np.ndarray) or not isinstance(img2, np.ndarray):
+            raise ValueError("Invalid input format!")
+        params = self._params()
+        exact = self._exact()                            # (raises for exact + alternate)
+        dev = _device_index(getattr(self, "device", None))
+        a, b = _check_pair(img1, img2)
+        if not (params[0] > 0 and params[0] % 2 == 1):
+            raise ValueError("winSize must be a positive odd number!")
+        H, W = a.shape[:2]
+        out = np.empty((H, W), np.int16)
+        if devices is not None:
+            arr, n = _device_list(devices)
+            rc = self._entry(lib, "multi", exact)[0](a.ctypes.data, b.ctypes.data, H, W, *params, out.ctypes.data, arr, n)
+        else:
+            rc = self._entry(lib, "host", exact)[0](a.ctypes.data, b.ctypes.data, H, W, *params, out.ctypes.data, dev)
+        if rc:
+            _native.check(rc, _INVALID)
+        if exact and devices is None:
+            self._warn_on_overflow(dev)
+        return out
+
+    def _compute_rectified_device(self, rig, raw1, raw2, interpolation=1):
+        """raw frames -> (rectification + the matcher's pixel records in one launch) -> matcher: ssamd_*_rectified_device"""
+        import torch
+        lib = _native.lib()
+        params = self._params()
+        if self._alternate(params[-1]):
+            raise ValueError("rectify=rig is not available with alternate=True")
+        exact = self._exact()
+        a, b = _check_pair_tensors(raw1, raw2)
+        if not (params[0] > 0 and params[0] % 2 == 1):
+            raise ValueError("winSize must be a positive odd number!")
+        if interpolation not in (0, 1):
+            raise NotImplementedError("only INTER_NEAREST (0) and INTER_LINEAR (1) are available")
+        if getattr(rig, "mapx1", None) is None:
+            raise ValueError("the rig has no rectification maps: call computeRectificationMaps() first")
+        mx1, my1 = rig._device_maps(1, a.device)
+        mx2, my2 = rig._device_maps(2, a.device)
+        if mx1.shape != mx2.shape:
+            raise ValueError("Wrong image dimensions!")
+        H, W = int(mx1.shape[0]), int(mx1.shape[1])
+        out = torch.empty((H, W), dtype=torch.int16, device=a.device)
+        _native.call_on_stream(a, self._entry(lib, "rectified", exact)[0], a.data_ptr(), b.data_ptr(), int(a.shape[0]), int(a.shape[1]),
+                               mx1.data_ptr(), my1.data_ptr(), mx2.data_ptr(), my2.data_ptr(), H, W, int(interpolation),
+                               *params, out.data_ptr(), invalid=_INVALID)
+        return out
+
+    def _match_device(self, t1, t2, out_row0, out_rows, row_parity, out, skip):
+        """the body of both ``_compute_device``"""
+        import torch
+        lib = _native.lib()
+        params = self._params()
+        a, b = _check_pair_tensors(t1, t2)
+        if not (params[0] > 0 and params[0] % 2 == 1):
+            raise ValueError("winSize must be a positive odd number!")
+        H, W = int(a.shape[0]), int(a.shape[1])
+        rows = H - out_row0 if out_rows is None else int(out_rows)
+        exact = self._exact()                            # (raises for exact + alternate)
+        if out is None:
+            out = torch.empty((rows, W), dtype=torch.int16, device=a.device)
+        elif out.dtype != torch.int16 or tuple(out.shape) != (rows, W) or not out.is_contiguous() or out.device != a.device:
+            raise ValueError("out must be a contiguous int16 [out_rows, W] tensor on the images' device")
+        if skip is not None and skip[1] > 0:
+            fn, ahead = self._entry(lib, "rows2", exact)[0], (int(skip[0]), int(skip[1]))
+        else:
+            fn, ahead = self._entry(lib, "device", exact, row_parity)
+        _native.call_on_stream(a, fn, a.data_ptr(), b.data_ptr(), H, W, int(out_row0), rows, *ahead, *params, out.data_ptr(),
+                               invalid=_INVALID)
+        return out
 
 
-class StereoASW():
+class StereoASW(_Matcher):
     """
     Adaptive Support-Weight stereo matching (K. Yoon, I. Kweon, 2006) -- drop-in for
     ``simplestereo.passive.StereoASW`` (reference ``passive.py:16-92``).
@@ -229,92 +328,14 @@ class StereoASW():
         except Exception:      # noqa: BLE001  -- a diagnostic must not fail the call
             pass
 
-    def compute(self, img1, img2, devices=None, rectify=None, interpolation=1):
-        """
-        Disparity map of a rectified BGR pair.
-
-        img1, img2: left and right image, ``numpy.uint8`` arrays ``[H, W, 3]`` in OpenCV channel
-        order (or two device tensors, see the module docstring).  Returns a new ``numpy.int16``
-        array ``[H, W]`` of left-referenced disparities.  ``devices`` (extension, host arrays only):
-        list of GPU indices that share the frame as row strips.
-
-        ``rectify`` (extension, device tensors only): a ``RectifiedStereoRig`` whose maps are computed -- ``img1`` / ``img2``
-        are then the RAW frames, and ``rig.rectifyImages(img1, img2, interpolation)`` followed by ``compute`` (the reference's
-        pipeline, examples/009) runs as one call in which rectification and Lab conversion are a single launch and the
-        rectified frames never exist in HBM.  Same map, bit for bit, as the two calls.
-        """
-        if rectify is not None:
-            if not (_is_device_tensor(img1) and _is_device_tensor(img2)) or devices is not None:
-                raise ValueError("rectify=rig applies to two device tensors (raw frames resident in HBM)")
-            if tuple(img1.shape) != tuple(img2.shape):
-                # cameras of different resolutions (res1 != res2, which rectifyImages supports): the fused launch takes one
-                # source size for both frames, so such rigs go through the two calls it otherwise replaces -- same map
-                return self.compute(*rectify.rectifyImages(img1, img2, interpolation))
-            return self._compute_rectified_device(rectify, img1, img2, interpolation)
-        if _is_device_tensor(img1) and _is_device_tensor(img2):
-            if devices is not None:
-                raise ValueError("devices=[...] applies to host arrays; device tensors are matched where they live")
-            return self._compute_device(img1, img2)
-        lib = _native.lib()
-        if not isinstance(img1, np.ndarray) or not isinstance(img2, np.ndarray):
-            raise ValueError("Invalid input format!")
-        win, maxd, mind, gc, gp, cons = self._params()
-        exact = self._exact()                            # (raises for exact + alternate)
-        dev = _device_index(getattr(self, "device", None))
-        a, b = _check_pair(img1, img2)
-        if not (win > 0 and win % 2 == 1):
-            raise ValueError("winSize must be a positive odd number!")
-        H, W = a.shape[:2]
-        out = np.empty((H, W), np.int16)
-        try:
-            if devices is not None:
-                arr, n = _device_list(devices)
-                multi = lib.ssamd_asw_alternate_multi if self._alternate(cons) else (lib.ssamd_asw_exact_multi if exact else lib.ssamd_asw_multi)
-                _native.check(multi(a.ctypes.data, b.ctypes.data, H, W, win, maxd, mind, gc, gp, cons, out.ctypes.data, arr, n))
-                return out
-            if self._alternate(cons):
-                _native.check(lib.ssamd_asw_alternate(a.ctypes.data, b.ctypes.data, H, W, win, maxd, mind, gc, gp, cons,
-                                                      out.ctypes.data, dev))
-                return out
-            op = lib.ssamd_asw_exact if exact else lib.ssamd_asw
-            _native.check(op(a.ctypes.data, b.ctypes.data, H, W, win, maxd, mind, gc, gp, cons, out.ctypes.data, dev))
-        except _native.NativeError as e:
-            _raise_native(e)
-        if exact:
-            self._warn_on_overflow(dev)
-        return out
-
-    def _compute_rectified_device(self, rig, raw1, raw2, interpolation=1):
-        """raw frames -> (rectification + Lab records in one launch) -> matcher: ssamd_asw_rectified_device"""
-        import torch
-        lib = _native.lib()
-        win, maxd, mind, gc, gp, cons = self._params()
-        if self._alternate(cons):
-            raise ValueError("rectify=rig is not available with alternate=True")
-        exact = self._exact()
-        a, b = _check_pair_tensors(raw1, raw2)
-        if not (win > 0 and win % 2 == 1):
-            raise ValueError("winSize must be a positive odd number!")
-        if interpolation not in (0, 1):
-            raise NotImplementedError("only INTER_NEAREST (0) and INTER_LINEAR (1) are available")
-        if getattr(rig, "mapx1", None) is None:
-            raise ValueError("the rig has no rectification maps: call computeRectificationMaps() first")
-        mx1, my1 = rig._device_maps(1, a.device)
-        mx2, my2 = rig._device_maps(2, a.device)
-        if mx1.shape != mx2.shape:
-            raise ValueError("Wrong image dimensions!")
-        H, W = int(mx1.shape[0]), int(mx1.shape[1])
-        out = torch.empty((H, W), dtype=torch.int16, device=a.device)
-        with torch.cuda.device(a.device):
-            stream = torch.cuda.current_stream(a.device).cuda_stream
-            try:
-                op = lib.ssamd_asw_exact_rectified_device if exact else lib.ssamd_asw_rectified_device
-                _native.check(op(a.data_ptr(), b.data_ptr(), int(a.shape[0]), int(a.shape[1]),
-                                 mx1.data_ptr(), my1.data_ptr(), mx2.data_ptr(), my2.data_ptr(), H, W,
-                                 int(interpolation), win, maxd, mind, gc, gp, cons, out.data_ptr(), ctypes.c_void_p(stream)))
-            except _native.NativeError as e:
-                _raise_native(e)
-        return out
+    def _entry(self, lib, route, exact, row_parity=0):
+        if getattr(self, "alternate", False):
+            if route == "rows2":
+                raise ValueError("two row ranges: not with alternate=True")
+            if route == "device":
+                return lib.ssamd_asw_alternate_rows_device, (int(row_parity) & 1,)
+            return getattr(lib, "ssamd_asw_alternate" + self._ROUTES[route]), ()
+        return getattr(lib, ("ssamd_asw_exact" if exact else "ssamd_asw") + self._ROUTES[route]), ()
 
     def _compute_device(self, t1, t2, out_row0=0, out_rows=None, row_parity=0, out=None, skip=None):
         """Operands already in HBM (torch tensors): returns a torch.int16 tensor on the device.
@@ -323,44 +344,10 @@ class StereoASW():
         sub-image carries ``winSize // 2 + 1`` halo rows.  ``out``: a contiguous int16 [out_rows, W] tensor to write into
         instead of a new one.  ``skip = (row, n)``: rows [row, row + n) of the range are left untouched in ``out`` and the two
         bands either side of them run as ONE launch (``ssamd_asw_device_rows2``; row strips, strips.py)."""
-        import torch
-        lib = _native.lib()
-        win, maxd, mind, gc, gp, cons = self._params()
-        a, b = _check_pair_tensors(t1, t2)
-        if not (win > 0 and win % 2 == 1):
-            raise ValueError("winSize must be a positive odd number!")
-        H, W = int(a.shape[0]), int(a.shape[1])
-        rows = H - out_row0 if out_rows is None else int(out_rows)
-        alt = self._alternate(cons)
-        exact = self._exact()                            # (raises for exact + alternate)
-        if out is None:
-            out = torch.empty((rows, W), dtype=torch.int16, device=a.device)
-        elif out.dtype != torch.int16 or tuple(out.shape) != (rows, W) or not out.is_contiguous() or out.device != a.device:
-            raise ValueError("out must be a contiguous int16 [out_rows, W] tensor on the images' device")
-        with torch.cuda.device(a.device):
-            stream = torch.cuda.current_stream(a.device).cuda_stream
-            try:
-                if skip is not None and skip[1] > 0:
-                    if alt:
-                        raise ValueError("two row ranges: not with alternate=True")
-                    op = lib.ssamd_asw_exact_device_rows2 if exact else lib.ssamd_asw_device_rows2
-                    _native.check(op(a.data_ptr(), b.data_ptr(), H, W, int(out_row0), rows, int(skip[0]), int(skip[1]),
-                                     win, maxd, mind, gc, gp, cons, out.data_ptr(), ctypes.c_void_p(stream)))
-                    return out
-                if alt:
-                    _native.check(lib.ssamd_asw_alternate_rows_device(a.data_ptr(), b.data_ptr(), H, W, int(out_row0), rows,
-                                                                      int(row_parity) & 1, win, maxd, mind, gc, gp, cons,
-                                                                      out.data_ptr(), ctypes.c_void_p(stream)))
-                    return out
-                op = lib.ssamd_asw_exact_device if exact else lib.ssamd_asw_device
-                _native.check(op(a.data_ptr(), b.data_ptr(), H, W, int(out_row0), rows, win, maxd, mind, gc, gp, cons, out.data_ptr(),
-                                 ctypes.c_void_p(stream)))
-            except _native.NativeError as e:
-                _raise_native(e)
-        return out
+        return self._match_device(t1, t2, out_row0, out_rows, row_parity, out, skip)
 
 
-class StereoGSW():
+class StereoGSW(_Matcher):
     """
     Geodesic Support-Weight matching as implemented by the reference
     (``simplestereo.passive.StereoGSW``, reference ``passive.py:99-158``): left- and
@@ -404,99 +391,10 @@ class StereoGSW():
         return (_c_int(self.winSize), _c_int(self.maxDisparity), _c_int(self.minDisparity), _c_int(self.gamma),
                 _c_double(self.fMax), _c_int(self.iterations), _c_int(self.bins))
 
-    def compute(self, img1, img2, devices=None, rectify=None, interpolation=1):
-        """Disparity map of a rectified 3-channel pair (uint8 [H,W,3]); returns int16 [H,W].
-        ``devices`` (extension, host arrays only): list of GPU indices that share the frame as row strips.
-        ``rectify`` (extension, device tensors only): a ``RectifiedStereoRig`` with computed maps -- ``img1`` / ``img2`` are then
-        the RAW frames, rectified and matched in one call (see ``StereoASW.compute``); same map as the two calls."""
-        if rectify is not None:
-            if not (_is_device_tensor(img1) and _is_device_tensor(img2)) or devices is not None:
-                raise ValueError("rectify=rig applies to two device tensors (raw frames resident in HBM)")
-            if tuple(img1.shape) != tuple(img2.shape):
-                # cameras of different resolutions (res1 != res2, which rectifyImages supports): the fused launch takes one
-                # source size for both frames, so such rigs go through the two calls it otherwise replaces -- same map
-                return self.compute(*rectify.rectifyImages(img1, img2, interpolation))
-            return self._compute_rectified_device(rectify, img1, img2, interpolation)
-        if _is_device_tensor(img1) and _is_device_tensor(img2):
-            if devices is not None:
-                raise ValueError("devices=[...] applies to host arrays; device tensors are matched where they live")
-            return self._compute_device(img1, img2)
-        lib = _native.lib()
-        if not isinstance(img1, np.ndarray) or not isinstance(img2, np.ndarray):
-            raise ValueError("Invalid input format!")
-        win, maxd, mind, gamma, fmax, it, bins = self._params()
-        dev = _device_index(getattr(self, "device", None))
-        a, b = _check_pair(img1, img2)
-        if not (win > 0 and win % 2 == 1):
-            raise ValueError("winSize must be a positive odd number!")
-        H, W = a.shape[:2]
-        out = np.empty((H, W), np.int16)
-        try:
-            if devices is not None:
-                arr, n = _device_list(devices)
-                _native.check(lib.ssamd_gsw_multi(a.ctypes.data, b.ctypes.data, H, W, win, maxd, mind, gamma, fmax, it,
-                                                  bins, out.ctypes.data, arr, n))
-                return out
-            _native.check(lib.ssamd_gsw(a.ctypes.data, b.ctypes.data, H, W, win, maxd, mind, gamma, fmax, it, bins,
-                                        out.ctypes.data, dev))
-        except _native.NativeError as e:
-            _raise_native(e)
-        return out
-
-    def _compute_rectified_device(self, rig, raw1, raw2, interpolation=1):
-        """raw frames -> (rectification + pixel packing in one launch) -> matcher: ssamd_gsw_rectified_device"""
-        import torch
-        lib = _native.lib()
-        win, maxd, mind, gamma, fmax, it, bins = self._params()
-        a, b = _check_pair_tensors(raw1, raw2)
-        if not (win > 0 and win % 2 == 1):
-            raise ValueError("winSize must be a positive odd number!")
-        if interpolation not in (0, 1):
-            raise NotImplementedError("only INTER_NEAREST (0) and INTER_LINEAR (1) are available")
-        if getattr(rig, "mapx1", None) is None:
-            raise ValueError("the rig has no rectification maps: call computeRectificationMaps() first")
-        mx1, my1 = rig._device_maps(1, a.device)
-        mx2, my2 = rig._device_maps(2, a.device)
-        if mx1.shape != mx2.shape:
-            raise ValueError("Wrong image dimensions!")
-        H, W = int(mx1.shape[0]), int(mx1.shape[1])
-        out = torch.empty((H, W), dtype=torch.int16, device=a.device)
-        with torch.cuda.device(a.device):
-            stream = torch.cuda.current_stream(a.device).cuda_stream
-            try:
-                _native.check(lib.ssamd_gsw_rectified_device(a.data_ptr(), b.data_ptr(), int(a.shape[0]), int(a.shape[1]),
-                                                             mx1.data_ptr(), my1.data_ptr(), mx2.data_ptr(), my2.data_ptr(), H, W,
-                                                             int(interpolation), win, maxd, mind, gamma, fmax, it, bins, out.data_ptr(),
-                                                             ctypes.c_void_p(stream)))
-            except _native.NativeError as e:
-                _raise_native(e)
-        return out
+    def _entry(self, lib, route, exact, row_parity=0):
+        return getattr(lib, "ssamd_gsw" + self._ROUTES[route]), ()
 
     def _compute_device(self, t1, t2, out_row0=0, out_rows=None, out=None, skip=None):
         """see StereoASW._compute_device: ``out`` = a contiguous int16 [out_rows, W] tensor to write into, ``skip = (row, n)`` =
         rows left untouched between two bands (``ssamd_gsw_device_rows2``; the overlapped strip step of strips.py)"""
-        import torch
-        lib = _native.lib()
-        win, maxd, mind, gamma, fmax, it, bins = self._params()
-        a, b = _check_pair_tensors(t1, t2)
-        if not (win > 0 and win % 2 == 1):
-            raise ValueError("winSize must be a positive odd number!")
-        H, W = int(a.shape[0]), int(a.shape[1])
-        rows = H - out_row0 if out_rows is None else int(out_rows)
-        if out is None:
-            out = torch.empty((rows, W), dtype=torch.int16, device=a.device)
-        elif out.dtype != torch.int16 or tuple(out.shape) != (rows, W) or not out.is_contiguous() or out.device != a.device:
-            raise ValueError("out must be a contiguous int16 [out_rows, W] tensor on the images' device")
-        with torch.cuda.device(a.device):
-            stream = torch.cuda.current_stream(a.device).cuda_stream
-            try:
-                if skip is not None and skip[1] > 0:
-                    _native.check(lib.ssamd_gsw_device_rows2(a.data_ptr(), b.data_ptr(), H, W, int(out_row0), rows, int(skip[0]), int(skip[1]),
-                                                             win, maxd, mind, gamma, fmax, it, bins, out.data_ptr(), ctypes.c_void_p(stream)))
-                    return out
-                _native.check(lib.ssamd_gsw_device(a.data_ptr(), b.data_ptr(), H, W, int(out_row0), rows, win,
-                                                   maxd, mind, gamma, fmax, it, bins, out.data_ptr(),
-                                                   ctypes.c_void_p(stream)))
-            except _native.NativeError as e:
-                _raise_native(e)
-        return out
+        return self._match_device(t1, t2, out_row0, out_rows, 0, out, skip)

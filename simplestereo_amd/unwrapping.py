@@ -72,25 +72,17 @@ Extensions (not in the reference): a CUDA/HIP ``torch.float64`` tensor
 ``infiniteImpulseResponseBatch`` unwraps ``[n, h, w]`` maps (host or device) in
 one launch, one workgroup per map.
 """
-import ctypes
 import operator
 
 import numpy as np
 
 from . import _native
-from .passive import _is_device_tensor
+from ._native import c_double as _c_double, is_device_tensor as _is_device_tensor
 
 __all__ = ["infiniteImpulseResponse", "infiniteImpulseResponseBatch", "unwrap", "unwrap2D"]
 
 
-def _c_double(v):
-    """PyArg_ParseTuple 'd': a float, an int (bool included) or anything with __float__ / __index__; not a string."""
-    if isinstance(v, (str, bytes, bytearray)):
-        raise ValueError("Invalid input format!")
-    try:
-        return float(v)
-    except (TypeError, ValueError, OverflowError):
-        raise ValueError("Invalid input format!") from None
+_INVALID = (_native.EINVAL, _native.ELIMIT)          # np.unwrap's forms: both are the caller's to fix
 
 
 def _check(phase, tau, ndim):
@@ -105,18 +97,6 @@ def _check(phase, tau, ndim):
     return t
 
 
-def _raise_native(e):
-    if e.code == -1:          # SSAMD_EINVAL
-        raise ValueError(e.message) from None
-    raise e
-
-
-def _raise_native_np(e):
-    if e.code in (-1, -5):    # SSAMD_EINVAL, SSAMD_ELIMIT
-        raise ValueError(e.message) from None
-    raise e
-
-
 def _run(phase, tau, ndim):
     t = _check(phase, tau, ndim)
     shape = tuple(int(s) for s in phase.shape)
@@ -125,29 +105,9 @@ def _run(phase, tau, ndim):
         import torch
         if phase.dtype != torch.float64:
             raise TypeError("phase must be a float64 tensor")
-        src = phase.contiguous()
-        out = torch.empty(shape, dtype=torch.float64, device=src.device)
-        if n == 0 or h == 0 or w == 0:
-            return out
-        with torch.cuda.device(src.device):
-            stream = torch.cuda.current_stream(src.device).cuda_stream
-            try:
-                _native.check(_native.lib().ssamd_iir_unwrap_device(src.data_ptr(), n, h, w, t, out.data_ptr(),
-                                                                    ctypes.c_void_p(stream)))
-            except _native.NativeError as e:
-                _raise_native(e)
-        return out
-    if phase.dtype != np.float64:
+    elif phase.dtype != np.float64:
         raise TypeError("phase must be a float64 array (the reference reads any buffer as doubles)")
-    src = np.ascontiguousarray(phase)
-    out = np.empty(shape, dtype=np.float64)
-    if n == 0 or h == 0 or w == 0:
-        return out
-    try:
-        _native.check(_native.lib().ssamd_iir_unwrap(src.ctypes.data, n, h, w, t, out.ctypes.data, -1))
-    except _native.NativeError as e:
-        _raise_native(e)
-    return out
+    return _native.run("ssamd_iir_unwrap", (phase,), shape, lambda src, out: (src, n, h, w, t, out), (_native.EINVAL,))
 
 
 def infiniteImpulseResponse(phase, tau=1):
@@ -184,7 +144,7 @@ def infiniteImpulseResponseBatch(phases, tau=1):
 
 
 def _fp64_input(p, name):
-    """-> (is a device tensor, contiguous float64 input); TypeError otherwise"""
+    """TypeError unless p is a float64 ndarray or device tensor"""
     dev = _is_device_tensor(p)
     if not (dev or isinstance(p, np.ndarray)):
         raise TypeError("%s must be a float64 ndarray or a CUDA/HIP torch.float64 tensor" % name)
@@ -192,37 +152,8 @@ def _fp64_input(p, name):
         import torch
         if p.dtype != torch.float64:
             raise TypeError("%s must be a float64 tensor (this path is fp64 only)" % name)
-        return True, p
-    if p.dtype != np.float64:
+    elif p.dtype != np.float64:
         raise TypeError("%s must be a float64 array (this path is fp64 only)" % name)
-    return False, p
-
-
-def _np_run(dev, p, shape, host_call, device_call):
-    """Allocate the result like p and run one of the two native calls on contiguous data (none for an empty array)."""
-    empty = any(s == 0 for s in shape)
-    if dev:
-        import torch
-        src = p.contiguous()
-        out = torch.empty(shape, dtype=torch.float64, device=src.device)
-        if empty:
-            return out
-        with torch.cuda.device(src.device):
-            stream = torch.cuda.current_stream(src.device).cuda_stream
-            try:
-                _native.check(device_call(_native.lib(), src.data_ptr(), out.data_ptr(), ctypes.c_void_p(stream)))
-            except _native.NativeError as e:
-                _raise_native_np(e)
-        return out
-    src = np.ascontiguousarray(p)
-    out = np.empty(shape, dtype=np.float64)
-    if empty:
-        return out
-    try:
-        _native.check(host_call(_native.lib(), src.ctypes.data, out.ctypes.data))
-    except _native.NativeError as e:
-        _raise_native_np(e)
-    return out
 
 
 def unwrap(p, discont=None, axis=-1, *, period=2 * np.pi):
@@ -250,7 +181,7 @@ def unwrap(p, discont=None, axis=-1, *, period=2 * np.pi):
     """
     if isinstance(p, np.generic):                      # a numpy scalar is a 0-d array to numpy
         p = np.asarray(p)
-    dev, p = _fp64_input(p, "p")
+    _fp64_input(p, "p")
     if p.ndim == 0:
         raise ValueError("diff requires input that is at least one dimensional")
     ax = operator.index(axis)
@@ -270,9 +201,7 @@ def unwrap(p, discont=None, axis=-1, *, period=2 * np.pi):
     outer = int(np.prod(shape[:ax], dtype=object)) if ax else 1
     inner = int(np.prod(shape[ax + 1:], dtype=object)) if ax + 1 < len(shape) else 1
     n = shape[ax]
-    return _np_run(dev, p, shape,
-                   lambda L, src, out: L.ssamd_np_unwrap(src, outer, n, inner, dis, per, out, -1),
-                   lambda L, src, out, stream: L.ssamd_np_unwrap_device(src, outer, n, inner, dis, per, out, stream))
+    return _native.run("ssamd_np_unwrap", (p,), shape, lambda src, out: (src, outer, n, inner, dis, per, out), _INVALID)
 
 
 def unwrap2D(phase):
@@ -284,13 +213,11 @@ def unwrap2D(phase):
     its own.  Returns the same shape, equal bit for bit to
     ``np.unwrap(np.unwrap(phase, discont=np.pi, axis=-1), discont=np.pi, axis=-2)``.
     """
-    dev, phase = _fp64_input(phase, "phase")
+    _fp64_input(phase, "phase")
     if phase.ndim not in (2, 3):
         raise ValueError("phase must be [h, w] or [n, h, w]")
     shape = tuple(int(s) for s in phase.shape)
     if max(shape) > 2 ** 31 - 1:
         raise ValueError("phase extents beyond 2^31 - 1 are not supported")
     n, h, w = (1,) + shape if phase.ndim == 2 else shape
-    return _np_run(dev, phase, shape,
-                   lambda L, src, out: L.ssamd_np_unwrap_xy(src, n, h, w, out, -1),
-                   lambda L, src, out, stream: L.ssamd_np_unwrap_xy_device(src, n, h, w, out, stream))
+    return _native.run("ssamd_np_unwrap_xy", (phase,), shape, lambda src, out: (src, n, h, w, out), _INVALID)
