@@ -28,7 +28,7 @@
 // contraction -- so even candidates that differ in the last ulp of 40 (1 - k ulp) (every tap saturated:
 // profiles/r05_exact_mode_audit.txt) resolve as in the reference.  What can still differ: a candidate the fp32 kernels put
 // more than the near-tie band from their winner although it wins in fp64 (none seen; the band grows with the window,
-// ssamd_api.hip), and a queue overflow (counted, reported, the fp32 map is kept).
+// host_asw_exact.h), and a queue overflow (counted, reported, the fp32 map is kept).
 #pragma once
 #include "asw_shared.hip.h"
 #include "lab_kernels.hip.h"

@@ -1,6 +1,6 @@
 // Launch planner of the ASW kernels: tile layouts in LDS, the cost model that picks a tile and a kernel form, the wave kernel's
 // strip.  Pure integer / double arithmetic: a function of its arguments (shape, window, PlanOptions) -- no HIP call, no global,
-// no tune(): the options come in with the caller.  The per-shape caches and the autotuner live with the operators (ssamd_api.hip), the only file that includes this
+// no tune(): the options come in with the caller.  The per-shape caches and the autotuner live with the operators (host_geometry.h, host_asw.h); host_context.h, a host section of ssamd_api.hip, is the only file that includes this
 // (behind asw_shared.hip.h and asw_wave_kernel.hip.h: AswGeom, AswWaveGeom, the register-tile constants and round_up are theirs).
 #pragma once
 

@@ -1,5 +1,5 @@
 // Host planner of the Fourier-profilometry phase kernel (ftp_kernels.hip.h): which DFT bins a row keeps, and the launch shape.
-// Pure arithmetic, like asw_plan.h and gsw_plan.h (ssamd_api.hip is the only file that includes it); needs no device.
+// Pure arithmetic, like asw_plan.h and gsw_plan.h (host_context.h, a host section of ssamd_api.hip, is the only file that includes it); needs no device.
 //
 // The reference masks the spectrum with numpy (active.py:681-722):
 //     freqs = np.fft.fftfreq(w);  G[(freqs - fmin) < 0] = 0;  G[(freqs - fmax) > 0] = 0

@@ -1,5 +1,5 @@
 // Launch planner of the GSW kernel: tile layout, cost model, autotuning candidates.  Pure arithmetic, like asw_plan.h (which it
-// follows in ssamd_api.hip, the only file that includes it).
+// follows in host_context.h, a host section of ssamd_api.hip and the only file that includes it).
 #pragma once
 
 bool gsw_layout(GswGeom &g, int win, int XG, int DG, int Ty, size_t limit, int Hy = 1)

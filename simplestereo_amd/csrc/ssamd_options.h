@@ -1,4 +1,4 @@
-// The SSAMD_* experiment / test hooks, each declared ONCE.  Included by ssamd_api.hip only, behind the kernel headers.
+// The SSAMD_* experiment / test hooks, each declared ONCE.  Included by host_context.h (a host section of ssamd_api.hip) only, behind the kernel headers.
 //   X(name, member of Tuning, type, value when unset, value parsed from the string v (never NULL), forces)
 // forces: a condition on the member's value x under which the option forces a kernel form -- such a call neither reads nor writes
 // the ASW geometry cache and is not autotuned (asw_geometry_forced).  SSAMD_ASW_STATIC and SSAMD_ASW_EVOL_MAX_MB force although

@@ -371,7 +371,7 @@ def test_exact_mode_mini_soak_against_the_oracle(ss):
 @pytest.mark.parametrize("win,H,W,maxd,cons", [(61, 40, 180, 24, False), (101, 36, 160, 12, True), (151, 30, 200, 10, False), (255, 20, 300, 6, False)])
 def test_large_windows_against_the_oracle(win, H, W, maxd, cons, ss):
     """the near-tie band was a fixed 128 key ulps whatever the window -- at winSize 35 the (N, S') sums have 1 225
-    fp32 terms, at the allowed 255 they have 65 025.  The band now grows with the window (ssamd_api.hip asw_exact_prepare); here
+    fp32 terms, at the allowed 255 they have 65 025.  The band now grows with the window (csrc/host_asw_exact.h asw_exact_prepare); here
     windows of 61 .. 255 on textured, quantised and mirrored content against the fp64 oracle: the maps are equal, and the fp32
     argmin alone stays inside north_star's tolerance."""
     from oracle import oracle

@@ -1,6 +1,6 @@
 """The launch planner's decisions are pinned: tests/golden/plan_cases.npz holds what ssamd_asw_geometry, ssamd_asw_kernel_form
 and ssamd_gsw_geometry answered, for a sweep of shapes under 21 ASW and 11 GSW option sets, BEFORE the planner moved out of
-ssamd_api.hip (tests/golden/make_golden_plan.py).  Host arithmetic only: no GPU."""
+the library's host code, then all in ssamd_api.hip (tests/golden/make_golden_plan.py).  Host arithmetic only: no GPU."""
 import importlib.util
 import json
 import os
