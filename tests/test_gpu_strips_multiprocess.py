@@ -58,8 +58,21 @@ def _worker(rank, world, port, case, q):
             want = m.compute(L, R)                           # whole frame, one process
         exp = params.get("_overlap")
         exp = exp[rank] if isinstance(exp, (list, tuple)) else exp
-        q.put((rank, bool(np.array_equal(full, want)) and (exp is None or ctx.overlap == exp),
-               int((full != want).sum()) if exp is None or ctx.overlap == exp else "overlap=%r" % ctx.overlap))
+        cut_ok = True
+        if params.get("_default_cut"):
+            # default mode: overlapped, and the interior launch is the halo-free rows cut to whole rounds of the device's workgroup slots
+            from simplestereo_amd import _native
+            halo_free = (r1 - r0) - (ctx.pad if ctx.h0 < r0 else 0) - (ctx.pad if ctx.h1 > r1 else 0)
+            g = _native.asw_geometry(W, halo_free, m.winSize, m.maxDisparity, m.minDisparity)
+            slots = torch.cuda.get_device_properties(dev).multi_processor_count * strips.resident_workgroups(g["threads"], g["lds_bytes"])
+            cut_ok = (ctx.overlap is True and 0 < ctx.interior <= halo_free and ctx.top + ctx.interior + ctx.bot == r1 - r0 and
+                      ctx.interior * g["grid_x"] * g["grid_z"] % slots == 0)
+            print("rank %d: top / interior / bot %d / %d / %d of %d halo-free rows, %d workgroups per row, %d slots" %
+                  (rank, ctx.top, ctx.interior, ctx.bot, halo_free, g["grid_x"] * g["grid_z"], slots), flush=True)
+        ok = exp is None or ctx.overlap == exp
+        q.put((rank, bool(np.array_equal(full, want)) and ok and cut_ok,
+               "overlap=%r" % ctx.overlap if not ok else int((full != want).sum()) if cut_ok else
+               "cut: overlap=%r top / interior / bot %d / %d / %d" % (ctx.overlap, ctx.top, ctx.interior, ctx.bot)))
     except Exception as e:      # noqa: BLE001
         q.put((rank, False, repr(e)))
     finally:
@@ -82,7 +95,9 @@ def _worker(rank, world, port, case, q):
     (3, ("asw", 96, 300, dict(winSize=35, maxDisparity=16, minDisparity=1, _overlap=[True, False, True]))),
     (2, ("asw", 100, 300, dict(winSize=35, maxDisparity=16, _overlap=True))),
     # default mode (interior launch cut to whole rounds of workgroups, the rest joins the border launch incl. its half-width last round)
-    (2, ("asw", 200, 1920, dict(winSize=35, maxDisparity=192))),
+    # and asserts the cut: no `force`, both ranks overlapped, the interior rows fill whole rounds (the smallest frame on which a
+    # 120-column, 12-wave tile fills at least one)
+    (2, ("asw", 200, 1920, dict(winSize=35, maxDisparity=192, _default_cut=True))),
     (3, ("asw", 47, 160, dict(winSize=11, maxDisparity=24, alternate=True))),      # strips of 16 / 16 / 15 rows: odd and even starts
     # BASELINE config 5's partition: eight ranks, 4096 columns, D 0..256, win 35 (the 88 x 260 tiles of the 4K launch); 136
     # rows = eight strips of 17 rows = exactly the halo, so every interior rank receives both halos whole from its neighbours

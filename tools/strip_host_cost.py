@@ -5,7 +5,8 @@ goes to this very process over RCCL (isend / irecv to self in one batched group)
 the interior launch, the border launch -- everything but the all_gather, which needs peers.  Reported per configuration:
   wall_ms        per step, device-synchronised once after the loop
   host_step_ms   CPU time inside step() per step (no synchronisation) -- the budget VERDICT r05 set is <= 0.25 ms
-  kernel_ms      aggregation kernels per step (interior + border launch), exchange_ms, exchange_exposed_ms (not hidden)
+  kernel_ms      aggregation kernels per step (interior + border launch) and their launches_per_step, exchange_ms,
+                 exchange_exposed_ms (not hidden)
 Not a scaling measurement: one GPU, the peer is the rank itself."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -61,7 +62,7 @@ for world, vrank in WORLDS:
             print(json.dumps({"case": name, "virtual_rank": "%d of %d" % (vrank, world), "strip_rows": r1 - r0, "overlapped": ctx.overlap,
                               "interior_rows": ctx.interior if ctx.overlap else None, "border_rows": (ctx.top + ctx.bot) if ctx.overlap else None,
                               "wall_ms": round(wall, 3), "host_step_ms": round(host, 3), "host_enqueue_of_%d_steps_ms" % n: round(host_loop * 1e3, 2),
-                              "kernel_ms": round(ms[slot] / 10, 3), "exact_pass_ms": round(ms[_native.K_ASW_EXACT] / 10, 3),
+                              "kernel_ms": round(ms[slot] / 10, 3), "launches_per_step": launches[slot] / 10, "exact_pass_ms": round(ms[_native.K_ASW_EXACT] / 10, 3),
                               "exchange_ms": round(ph.get("exchange_ms", 0.0), 3),
                               "exchange_exposed_ms": round(ph["exchange_exposed_ms"], 3) if "exchange_exposed_ms" in ph else None,
                               "host_step_ms_with_events": round(ph["host_step_ms"], 3)}), flush=True)
