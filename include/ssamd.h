@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define SSAMD_ABI_VERSION 8      /* 8 also carries ssamd_ftp_cloud / ssamd_ftp_cloud_device (pure additions, billed to SSAMD_K_REPROJECT); 8: ssamd_np_unwrap / _device / _xy / _xy_device / _plan, ssamd_ftp_phase* unwrap = 2 and profile slot SSAMD_K_NPUNWRAP; 7: ssamd_ftp_phase / ssamd_ftp_phase_device / ssamd_ftp_band and profile slot SSAMD_K_FTP; 6: ssamd_iir_unwrap / ssamd_iir_unwrap_device and profile slot SSAMD_K_UNWRAP; 5:ssamd_asw_exact_device_rows2 / _rectified_device (round 6: near-ties selected inside the aggregation kernels); 4: ssamd_asw_exact* (round 5); 3: GSW autotuning; 2: ssamd_set_option (round 3) + the multi-device and verification entry points added in round 2 */
+#define SSAMD_ABI_VERSION 8      /* 8 also carries ssamd_gsw_argmins (a pure addition) and ssamd_ftp_cloud / ssamd_ftp_cloud_device (pure additions, billed to SSAMD_K_REPROJECT); 8: ssamd_np_unwrap / _device / _xy / _xy_device / _plan, ssamd_ftp_phase* unwrap = 2 and profile slot SSAMD_K_NPUNWRAP; 7: ssamd_ftp_phase / ssamd_ftp_phase_device / ssamd_ftp_band and profile slot SSAMD_K_FTP; 6: ssamd_iir_unwrap / ssamd_iir_unwrap_device and profile slot SSAMD_K_UNWRAP; 5:ssamd_asw_exact_device_rows2 / _rectified_device (round 6: near-ties selected inside the aggregation kernels); 4: ssamd_asw_exact* (round 5); 3: GSW autotuning; 2: ssamd_set_option (round 3) + the multi-device and verification entry points added in round 2 */
 
 #define SSAMD_OK 0
 #define SSAMD_EINVAL (-1)     /* bad argument (message tells which)            */
@@ -359,6 +359,14 @@ int ssamd_asw_argmins(const uint8_t *img1, const uint8_t *img2, int height, int 
                       double gammaC, double gammaP,
                       int16_t *left_disparity, int16_t *right_match, int device);
 
+/* The same for GSW, whose left-right check and filling are unconditional (_passive.cpp:546 and 661-663): left_disparity[y][x] =
+ * x - dBest of the left-referenced pass (x when its candidate loop is empty or no candidate won: dBest stays 0),
+ * right_match[y][xr] = dBest of the right-referenced pass (0 when nothing won).  A wrong winner that the check
+ * invalidates and the filling paints over is invisible in the map of ssamd_gsw; it is not here. */
+int ssamd_gsw_argmins(const uint8_t *img1, const uint8_t *img2, int height, int width,
+                      int winSize, int maxDisparity, int minDisparity, int gamma, float fMax, int iterations, int bins,
+                      int16_t *left_disparity, int16_t *right_match, int device);
+
 /* CIELab conversion used by ASW (replaces ColorConversion::ImageFromBGR2Lab,
  * headers/colorconversion.hpp:81-86); float32 [height][width][3]. Host buffers. */
 int ssamd_bgr2lab(const uint8_t *img, int height, int width, float *lab, int device);
@@ -420,7 +428,9 @@ int ssamd_set_option(const char *name, const char *value);
  * pixels with near-ties, "exact_raw_entries" what the aggregation kernels of a merging call (several chunks / consistent) queued
  * against their tile-local winners before the filter, "exact_overflow" 1 when a candidate queue overflowed (the fp32 map was
  * kept); "pipe_persist_launches": phase-shifted launches in the persistent form (SSAMD_ASW_PERSIST), "pipe_persist_items": the tiles
- * those launches finished, counted on the device once per tile (synchronises the device).
+ * those launches finished, counted on the device once per tile (synchronises the device); "gsw_plain_calls": GSW calls that ran
+ * gsw_plain_kernel (gamma < 0, fMax < 0 or NaN, or SSAMD_GSW_PLAIN) instead of the tiled kernel -- those are not timed in slot
+ * SSAMD_K_GSW_AGG, which counts the tiled kernel's launches only.
  * SSAMD_EINVAL for an unknown name. */
 int ssamd_counter(int device, const char *name, long long *value);
 

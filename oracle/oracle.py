@@ -46,6 +46,8 @@ def _load():
         lib.oracle_gsw.restype = ctypes.c_int
         lib.oracle_gsw.argtypes = [u8p, u8p] + [ctypes.c_int] * 6 + [ctypes.c_float] + \
             [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_int16)]
+        lib.oracle_gsw_raw.restype = ctypes.c_int
+        lib.oracle_gsw_raw.argtypes = lib.oracle_gsw.argtypes + [ctypes.POINTER(ctypes.c_int16)] * 2
         lib.oracle_bgr2lab.restype = None
         lib.oracle_bgr2lab.argtypes = [u8p, ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int]
         _lib = lib
@@ -124,18 +126,22 @@ def asw_alternate(img1, img2, winSize=35, maxDisparity=16, minDisparity=0, gamma
 
 
 def gsw(img1, img2, winSize=11, maxDisparity=16, minDisparity=0, gamma=10, fMax=120,
-        iterations=3, bins=20, closed=False, nthreads=0):
-    """C restatement of ``_passive.computeGSW`` (reference _passive.cpp:703-774)."""
+        iterations=3, bins=20, closed=False, nthreads=0, return_raw=False):
+    """C restatement of ``_passive.computeGSW`` (reference _passive.cpp:703-774).  ``return_raw``: also the winners of the
+    two passes before the left-right step, ``(map, raw_left, raw_right)``: ``raw_left[y, x]`` = x - dBest of the
+    left-referenced pass (x when nothing won), ``raw_right[y, x]`` = dBest of the right-referenced one (0 when nothing won)."""
     lib = _load()
     a, b = _img(img1), _img(img2)
     H, W = a.shape[:2]
+    i16p = ctypes.POINTER(ctypes.c_int16)
     out = np.empty((H, W), np.int16)
-    rc = lib.oracle_gsw(_u8(a), _u8(b), H, W, winSize, maxDisparity, minDisparity, int(gamma),
-                        float(fMax), int(iterations), int(bins), int(bool(closed)), int(nthreads),
-                        out.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)))
+    raw = [np.empty((H, W), np.int16) for _ in range(2)] if return_raw else []
+    args = (_u8(a), _u8(b), H, W, winSize, maxDisparity, minDisparity, int(gamma), float(fMax), int(iterations), int(bins),
+            int(bool(closed)), int(nthreads), out.ctypes.data_as(i16p))
+    rc = lib.oracle_gsw_raw(*args, *[r.ctypes.data_as(i16p) for r in raw]) if return_raw else lib.oracle_gsw(*args)
     if rc != 0:
         raise RuntimeError("oracle_gsw failed rc=%d" % rc)
-    return out
+    return (out, raw[0], raw[1]) if return_raw else out
 
 
 def bgr2lab(img):

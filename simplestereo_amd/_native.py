@@ -47,6 +47,7 @@ _SIGNATURES = (
     ("ppiippppiii" + _GSW + "pp", "ssamd_gsw_rectified_device"),
     ("ppiiiiiddpi", "ssamd_asw_costs"),
     ("ppiiiiiddppi", "ssamd_asw_argmins"),
+    ("ppii" + _GSW + "ppi", "ssamd_gsw_argmins"),
     ("piipi", "ssamd_bgr2lab"),
     ("piippiiipp", "ssamd_remap_bgr_device"),
     ("piiDpp", "ssamd_reproject_device"),

@@ -361,6 +361,69 @@ __global__ __launch_bounds__(GSW_MAX_THREADS, 4) void gsw_aggregate_kernel(const
     }
 }
 
+// The reference's loops as they stand, one thread per (pass, output row, column): for the parameters the tiled kernel's
+// layout does not cover (host_gsw.h: gamma < 0, fMax < 0 or NaN) and, under SSAMD_GSW_PLAIN, as a second standard for
+// the tiled kernel's raw winners.  Weights in the closed form above, with what the tiled kernel leaves out: a cell the
+// relaxation never reaches ends at expf(-INFINITY / gamma) -- 0 for gamma > 0, +inf for gamma < 0 (w_unreached, computed
+// by the host with the table) -- and is tapped like any other, so that one inf weight makes the candidate's cost inf or
+// NaN.  Candidates and taps in the reference's order with its `continue` / `break` tests (_passive.cpp:502-543,
+// 624-659), unfused fp32 multiply and add, std::min(fMax, e) as (e < fMax) ? e : fMax, a float `cost < best` from
+// INFINITY: a NaN or inf cost never wins, a negative one does.  The key is written only when something won.
+struct GswPlainArgs {
+    const uint32_t *img[2];      // [H][W] packed left, right
+    const float *tab;            // [GSW_TAB_SIZE]
+    u64 *key[2];                 // [rows][W] per pass, preset to KEY_NONE
+    int H, W, win, pad, minD, maxD, row0, rows, iterations;
+    float fMax, w_unreached;
+};
+
+__device__ __forceinline__ uint32_t gsw_dist2_packed(uint32_t a, uint32_t b)
+{
+    return gsw_dist2(gsw_pix(a, 1.f, 0.f), gsw_pix(b, 1.f, 0.f));
+}
+
+__global__ __launch_bounds__(256) void gsw_plain_kernel(const GswPlainArgs A)
+{
+#pragma clang fp contract(off)
+    const int right = blockIdx.z, W = A.W, H = A.H, win = A.win, p = A.pad;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long long)A.rows * W) return;
+    const int x = (int)(idx % W), y = A.row0 + (int)(idx / W);
+    const uint32_t *const ref = A.img[right], *const tgt = A.img[1 - right];
+    const uint32_t centre = ref[(size_t)y * W + x];
+    const bool clipped = !right && x + p >= W;                   // left-pass break quirk: only the centre, and on row 0 its row
+    auto weight = [&](int i, int j) -> float {
+        const int yy = y - p + i, xx = x - p + j;
+        if (i == p && j == p) return 1.0f;                       // exp(-0 / gamma)
+        if (A.iterations <= 0 || yy < 0 || yy >= H || xx < 0 || xx >= W) return A.w_unreached;
+        if (clipped && !(y == 0 && yy == 0)) return A.w_unreached;
+        return A.tab[gsw_dist2_packed(ref[(size_t)yy * W + xx], centre)];
+    };
+    const int first = right ? x + A.minD : x - A.minD;           // target columns in the reference's order
+    const int last = right ? min(W - 1, x + A.maxD) : max(0, x - A.maxD), step = right ? 1 : -1;
+    float best = INFINITY;
+    int won = -1;
+    for (int d = first; right ? d <= last : d >= last; d += step) {
+        float cost = 0.f;
+        for (int i = 0; i < win; ++i) {
+            const int ii = y - p + i;
+            if (ii < 0) continue;
+            if (ii >= H) break;
+            for (int j = 0; j < win; ++j) {
+                const int kk = x - p + j, jj = d - p + j;
+                if (jj < 0 || kk < 0) continue;
+                if (jj >= W || kk >= W) break;
+                const float e = gsw_sqrt_int((float)gsw_dist2_packed(ref[(size_t)ii * W + kk], tgt[(size_t)ii * W + jj]));
+                const float capped = (e < A.fMax) ? e : A.fMax;
+                const float term = weight(i, j) * capped;
+                cost = cost + term;
+            }
+        }
+        if (cost < best) { best = cost; won = d; }
+    }
+    if (won >= 0) A.key[right][idx] = make_key(best, right ? (uint32_t)won : (uint32_t)(x - won));
+}
+
 // verification helper: gsw_sqrt_int over s = 0 .. n-1 (what = 1: the bare v_sqrt_f32, for the record of why it is not used)
 __global__ __launch_bounds__(256) void gsw_sqrt_probe_kernel(float *__restrict__ out, int n, int what)
 {

@@ -161,6 +161,7 @@ struct Ctx {
     long long tail_splits = 0;          // phase-shifted launches whose last partial round of workgroups ran as half-width tiles
     long long exact_calls = 0;          // ASW calls that ran the fp64 tie-break pass
     long long persist_launches = 0;     // phase-shifted launches in the persistent form
+    long long gsw_plain_calls = 0;      // GSW calls that ran gsw_plain_kernel instead of the tiled kernel (host_gsw.h)
     Profile prof;
 };
 

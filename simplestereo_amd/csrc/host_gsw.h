@@ -18,6 +18,7 @@ struct GswCall : MatchCall {
     int gamma = 0;
     float fMax = 0;
     int iterations = 0;
+    int16_t *d_raw_right = nullptr;     // verification dump (ssamd_gsw_argmins): both raw winners instead of the left-right check and filling
 };
 
 GswCall gsw_params(int H, int W, int win, int maxD, int minD, int gamma, float fMax, int iterations)      // (images, rows, output, stream: by field name)
@@ -62,6 +63,22 @@ int gsw_device_impl(Ctx &c, const GswCall &q)
                                    (uint32_t *)c.recR.ptr + (size_t)r0 * W, np);
             }
             HIP_TRY(hipGetLastError());
+        }
+        // The tiled kernel's layout assumes non-negative finite costs (its keys order cost bits as unsigned) and weight 0 for the
+        // cells the relaxation never reaches (a skipped tap is w * 0): true for gamma > 0 and a cap >= 0.  The rest -- and any
+        // call under SSAMD_GSW_PLAIN -- runs the reference's loops as they stand (gsw_plain_kernel), counted in gsw_plain_calls.
+        if (q.gamma < 0 || q.fMax < 0 || q.fMax != q.fMax || opts.gsw_plain) {
+            GswPlainArgs pa;
+            pa.img[0] = (const uint32_t *)c.recL.ptr; pa.img[1] = (const uint32_t *)c.recR.ptr;
+            pa.key[0] = (u64 *)c.keyL.ptr; pa.key[1] = (u64 *)c.keyR.ptr;
+            pa.tab = d_tab;
+            pa.H = H; pa.W = W; pa.win = win; pa.pad = p; pa.minD = minD; pa.maxD = maxD; pa.row0 = row0; pa.rows = rows;
+            pa.iterations = q.iterations; pa.fMax = q.fMax;
+            pa.w_unreached = expf(-INFINITY / q.gamma);
+            ++c.gsw_plain_calls;
+            hipLaunchKernelGGL(gsw_plain_kernel, dim3((unsigned)((nout + 255) / 256), 1, 2), dim3(256), 0, s, pa);
+            HIP_TRY(hipGetLastError());
+            return launch_finalize(c, SSAMD_K_GSW_FIN, true, 0, rows, W, q.d_disp, s, q.d_raw_right);
         }
         GswArgs a;
         if ((rc = gsw_choose_geometry(a.g, opts, W, rows, win, nD))) return rc;
@@ -114,6 +131,6 @@ int gsw_device_impl(Ctx &c, const GswCall &q)
             if ((rc = launch(final_geom))) return rc;
         }
     }
-    return launch_finalize(c, SSAMD_K_GSW_FIN, true, 0, rows, W, q.d_disp, s);   // consistency is unconditional in GSW
+    return launch_finalize(c, SSAMD_K_GSW_FIN, true, 0, rows, W, q.d_disp, s, q.d_raw_right);   // consistency is unconditional in GSW
 }
 }  // namespace

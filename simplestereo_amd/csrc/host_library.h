@@ -62,6 +62,7 @@ int ssamd_counter(int device, const char *name, long long *value)
     else if (n == "tail_splits") *value = c->tail_splits;
     else if (n == "exact_calls") *value = c->exact_calls;
     else if (n == "pipe_persist_launches") *value = c->persist_launches;
+    else if (n == "gsw_plain_calls") *value = c->gsw_plain_calls;
     else if (n == "pipe_persist_items") {
         // tiles finished by persistent phase-shifted launches on this device so far (counted on the device, once per finished item)
         unsigned long long done = 0;

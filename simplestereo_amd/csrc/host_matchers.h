@@ -9,7 +9,7 @@ struct HostJob {
     const uint8_t *img1 = nullptr, *img2 = nullptr;      // the two host images, whole
     int16_t *disparity = nullptr;  // full-image outputs: [H][W],
     float *costs = nullptr;        // ... the cost dump (ssamd_asw_costs),
-    int16_t *raw_right = nullptr;  // ... the raw right-referenced matches (verification dump of ssamd_asw_argmins)
+    int16_t *raw_right = nullptr;  // ... the raw right-referenced matches (verification dump of ssamd_asw_argmins / ssamd_gsw_argmins)
     int o0 = 0, o1 = 0;            // output rows of the full image
     bool is_gsw = false;           // which of the two holds the parameters: H x W the whole image, no buffers, rows or stream
     AswCall asw;
@@ -46,6 +46,7 @@ int host_rows(const HostJob &j, int device)
     q.H = in1 - in0; q.row0 = j.o0 - in0; q.rows = rows;
     q.d_disp = (int16_t *)c->disp.ptr; q.s = s;
     if (j.is_gsw) {
+        g.d_raw_right = j.raw_right ? (int16_t *)c->lab.ptr : nullptr;
         rc = gsw_device_impl(*c, g);
     } else if (alternate) {            // (no exact pass and no dumps in this mode: left unset)
         a.exact = false;
@@ -299,6 +300,17 @@ int ssamd_gsw(const uint8_t *img1, const uint8_t *img2, int height, int width, i
     (void)bins;
     if (!img1 || !img2 || !disparity) return fail(SSAMD_EINVAL, "NULL buffer");
     return host_rows(HostJob(img1, img2, disparity, gsw_params(height, width, winSize, maxDisparity, minDisparity, gamma, fMax, iterations)), device);
+}
+
+int ssamd_gsw_argmins(const uint8_t *img1, const uint8_t *img2, int height, int width, int winSize, int maxDisparity,
+                      int minDisparity, int gamma, float fMax, int iterations, int bins, int16_t *left_disparity,
+                      int16_t *right_match, int device)
+{
+    (void)bins;
+    if (!img1 || !img2 || !left_disparity || !right_match) return fail(SSAMD_EINVAL, "NULL buffer");
+    HostJob j(img1, img2, left_disparity, gsw_params(height, width, winSize, maxDisparity, minDisparity, gamma, fMax, iterations));
+    j.raw_right = right_match;
+    return host_rows(j, device);
 }
 
 int ssamd_gsw_multi(const uint8_t *img1, const uint8_t *img2, int height, int width, int winSize, int maxDisparity,

@@ -8,6 +8,7 @@
 #define SSAMD_OPTIONS(X) \
     X("SSAMD_ASW_GEOM", asw_geom, std::string, "", v, !x.empty())   /* "XG,DG[,JC[,RX]]" / "XG,DG[,Ty[,Hy]]": forced launch geometry ("" = unset) */ \
     X("SSAMD_GSW_GEOM", gsw_geom, std::string, "", v, false) \
+    X("SSAMD_GSW_PLAIN", gsw_plain, int, 0, atoi(v) != 0 ? 1 : 0, false)   /* 1: every GSW call runs gsw_plain_kernel, the reference's loops one thread per pixel (tests: a second standard for the tiled kernel's raw winners) */ \
     X("SSAMD_ASW_PIPE", asw_pipe, int, -1, atoi(v), x >= 0)   /* -1 unset, 0: phase-shifted kernel off, 8 / 16: forced chunk length */ \
     X("SSAMD_ASW_DEPHASE", asw_dephase, int, -1, atoi(v), x >= 0)   /* -1 unset, else the wave order of the phase-shifted kernel */ \
     X("SSAMD_ASW_EVOL", asw_evol, int, 1, atoi(v), x != 1)   /* 0: in-kernel e tiles instead of the TAD volume */ \

@@ -28,7 +28,9 @@ reference reads them as if contiguous), negative ``minDisparity`` is rejected
 ``ValueError`` (the reference computes with any value, ``_passive.cpp:47-50``: a negative gamma turns the support
 weights into GROWING exponentials whose products overflow fp32 where the reference's fp64 does not, a zero gamma
 makes every cost NaN -- neither is a matcher anyone runs; ``StereoGSW`` accepts negative ``gamma`` like the
-reference, golden G9f).
+reference: window cells its relaxation never reaches then weigh exp(+inf) = inf and disqualify every candidate that taps
+one, and an inf or NaN cost never wins.  Such calls, and a negative or NaN ``fMax``, run a plain one-thread-per-pixel
+kernel that restates the reference's loops instead of the tiled one; golden G9f, tests/test_gpu_gsw_raw.py).
 
 Extensions (not in the reference): ``compute`` also accepts two CUDA/HIP
 ``torch.uint8`` tensors ``[H,W,3]`` already resident in HBM and then returns a

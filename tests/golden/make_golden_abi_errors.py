@@ -6,7 +6,8 @@ Most calls break two rules at once, so that what is recorded is the ORDER of the
 call fails, or returns 0 for an empty job, before a kernel is launched; the matcher checks run behind the device context, so a GPU
 is needed.  The library asked is the one ``simplestereo_amd._native`` loads -- the tree's own ``libssamd.so``, or another build of
 the same ABI named by ``SSAMD_LIB`` (with ``SSAMD_EXPERIMENT=1``).  The committed fixture was taken from the commit BEFORE the host
-side of the library was cut into sections.
+side of the library was cut into sections.  The two rows of ``ssamd_gsw_argmins`` were added with that entry point; recording them changed no
+other row.
 
 Writes ``abi_errors.json``: one row {"family", "entry", "args", "rc", "error"} per call; "error" is null where rc is 0 (the
 library keeps the previous call's message then).  ``tests/test_gpu_abi_errors.py`` repeats the calls and wants every row back.
@@ -175,6 +176,8 @@ def _cases():
     add("host_matchers", "ssamd_asw_argmins", HOST, HOST, H, W, 4, 3, 4, 5.0, 17.5, OUT, NULL, -1)
     add("host_matchers", "ssamd_asw_argmins", HOST, HOST, H, W, 4, 3, 4, 5.0, 17.5, OUT, OUT, -1)
     add("host_matchers", "ssamd_asw_argmins", HOST, HOST, H, W, 5, 4, 0, 0.0, 17.5, OUT, OUT, -1)
+    add("host_matchers", "ssamd_gsw_argmins", HOST, HOST, H, W, *_with(GSW, win=4), OUT, NULL, -1)
+    add("host_matchers", "ssamd_gsw_argmins", HOST, HOST, H, W, *_with(GSW, win=4), OUT, OUT, -1)
     # (..., disparity, devices, n_devices)
     for tail, entries in ((ASW, "ssamd_asw_multi ssamd_asw_exact_multi ssamd_asw_alternate_multi"), (GSW, "ssamd_gsw_multi")):
         add("host_matchers", entries, HOST, HOST, H, W, *_with(tail, win=4), OUT, ["ints", [0]], 0)
