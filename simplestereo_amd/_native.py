@@ -1,4 +1,4 @@
-"""ctypes binding of libssamd.so (C ABI in include/ssamd.h).
+"""ctypes binding of libssamd.so (C ABI in include/ssamd.h and include/ssamd_active.h).
 
 This is the only place Python touches the native library.  There is no Python or
 CPU fallback for the operators: if the library is missing, or no HIP device is
@@ -20,6 +20,7 @@ if os.environ.get("SSAMD_LIB"):
                           "library" % os.environ["SSAMD_LIB"])
     LIB_PATH = os.environ["SSAMD_LIB"]
 ABI_VERSION = 8
+ACTIVE_VERSION = 1         # SSAMD_ACTIVE_VERSION of include/ssamd_active.h, the second public header of the same library
 
 (K_LAB, K_ASW_AGG, K_ASW_FIN, K_GSW_AGG, K_GSW_FIN, K_REMAP, K_REPROJECT, K_ASW_ALT, K_ASW_EXACT, K_UNWRAP, K_FTP,
  K_NPUNWRAP, K_COUNT) = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12
@@ -68,6 +69,9 @@ _SIGNATURES = (
     ("piiip", "ssamd_np_unwrap_xy"),
     ("pipiiippidp", "ssamd_ftp_phase"),
     ("piiiipdp", "ssamd_ftp_cloud"),
+    # include/ssamd_active.h (SSAMD_ACTIVE_VERSION); tests/test_stereo_ftp_cpu.py holds these rows to that header
+    ("piiiiiipp", "ssamd_ftp_reference"),
+    ("piiiip", "ssamd_stripe_centroids"),
 ) for last, suffix in (("i", ""), ("p", "_device")))
 _RETURN_STRING = ("ssamd_last_error", "ssamd_kernel_name")
 _CTYPES = {"i": ctypes.c_int, "l": ctypes.c_longlong, "d": ctypes.c_double, "f": ctypes.c_float, "p": ctypes.c_void_p,
@@ -151,20 +155,20 @@ def call_on_stream(t, fn, *args, invalid=()):
             check(rc, invalid)
 
 
-def run(name, sources, shape, args, invalid=()):
+def run(name, sources, shape, args, invalid=(), dtype=np.float64):
     """The operator ``name`` on host arrays, or ``name + "_device"`` on device tensors (``sources``: all of one kind; made
-    contiguous): the float64 result of ``shape`` is allocated like them and returned as it is, without a native call, when an
-    extent is 0.  ``args(pointers of the sources ..., pointer of the result)`` gives every argument but the last, which is
+    contiguous): the result of ``shape`` and ``dtype`` (a numpy dtype; float64 by default) is allocated like them and returned
+    as it is, without a native call, when an extent is 0.  ``args(pointers of the sources ..., pointer of the result)`` gives every argument but the last, which is
     the current device (-1) or the current stream."""
     if is_device_tensor(sources[0]):
         import torch
         srcs = [s.contiguous() for s in sources]
-        out = torch.empty(shape, dtype=torch.float64, device=srcs[0].device)
+        out = torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device=srcs[0].device)
         if 0 not in shape:
             call_on_stream(out, getattr(lib(), name + "_device"), *args(*[s.data_ptr() for s in srcs], out.data_ptr()), invalid=invalid)
         return out
     srcs = [np.ascontiguousarray(s) for s in sources]
-    out = np.empty(shape, dtype=np.float64)
+    out = np.empty(shape, dtype=dtype)
     if 0 not in shape:
         check(getattr(lib(), name)(*args(*[s.ctypes.data for s in srcs], out.ctypes.data), -1), invalid)
     return out

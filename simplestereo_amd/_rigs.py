@@ -36,6 +36,7 @@ __all__ = ["StereoRig", "RectifiedStereoRig"]
 # OpenCV interpolation flag values, so callers can pass cv2.INTER_* or these
 INTER_NEAREST = 0
 INTER_LINEAR = 1
+INTER_CUBIC = 2
 
 
 def _dist_vector(d):
@@ -107,6 +108,57 @@ def _init_undistort_rectify_map(K, distCoeffs, R, newK, size):
     return mapx.astype(np.float32), mapy.astype(np.float32)
 
 
+_CUBIC_TABLE = None
+
+
+def _cubic_table():
+    """OpenCV's ``initInterTab2D(INTER_CUBIC, fixpt)`` as published (modules/imgproc/src/imgwarp.cpp): int16
+    ``[32 (fy), 32 (fx), 4 (tap row), 4 (tap column)]``, the 15-bit weights of ``cv2.remap(INTER_CUBIC)`` on 8-bit images.
+    OpenCV's source is not available where this is built, so every choice is stated, from its published arithmetic:
+
+    * ``interpolateCubic`` in float32 with ``A = -0.75`` at the fractions ``x = i / 32``: ``c0 = ((A(x+1) - 5A)(x+1) + 8A)(x+1) - 4A``,
+      ``c1 = ((A+2)x - (A+3))x x + 1``, ``c2`` = the same of ``1 - x``, ``c3 = 1 - c0 - c1 - c2`` (each operation is exact in
+      float32 at these fractions, so neither its order nor a fused multiply-add changes a bit);
+    * the float32 product ``c[fy][k1] * c[fx][k2]`` times 32768, rounded half to even and saturated to int16
+      (``saturate_cast<short>``): the one product that is 1.0, at the fractions (0, 0), becomes 32767 and the correction below
+      puts the missing 1 on tap (2, 2) -- still the identity on 8-bit values, ``(32767 a + b + 16384) >> 15 == a``;
+    * where the 16 weights do not sum to 32768, the difference is taken from ONE of them, searched over the taps
+      ``k1, k2 in {2, 3}`` (``ksize / 2 .. ksize / 2 + 1``, as OpenCV writes the loop -- not the four central taps 1..2): the
+      largest when the sum is short, the smallest when it is over; the scan starts with both at ``(2, 2)`` and tests "smaller
+      than the minimum" first and "larger than the maximum" only otherwise.
+
+    Which entry takes the correction is recalled, not verified: parity with cv2 stays unpinned (tests/test_cv2_pins_ftp.py
+    pins it wherever cv2 exists).  ``csrc/host_ftp_reference.h`` builds the same table for ``ftp_reference_kernel``."""
+    global _CUBIC_TABLE
+    if _CUBIC_TABLE is None:
+        f = np.float32
+        A = f(-0.75)
+        x = np.arange(32, dtype=np.float32) * f(1.0 / 32)
+        c = np.empty((32, 4), np.float32)
+        c[:, 0] = ((A * (x + f(1)) - f(5) * A) * (x + f(1)) + f(8) * A) * (x + f(1)) - f(4) * A
+        c[:, 1] = ((A + f(2)) * x - (A + f(3))) * x * x + f(1)
+        c[:, 2] = ((A + f(2)) * (f(1) - x) - (A + f(3))) * (f(1) - x) * (f(1) - x) + f(1)
+        c[:, 3] = f(1) - c[:, 0] - c[:, 1] - c[:, 2]
+        v = c[:, None, :, None] * c[None, :, None, :]                      # [fy, fx, k1, k2], float32 products
+        tab = np.clip(np.rint(v * f(32768)).astype(np.int64), -32768, 32767)      # saturate_cast<short>: 1.0 -> 32767
+        for i in range(32):
+            for j in range(32):
+                t = tab[i, j]
+                diff = int(t.sum()) - 32768
+                if diff == 0:
+                    continue
+                mn = mx = (2, 2)
+                for k in ((2, 2), (2, 3), (3, 2), (3, 3)):
+                    if t[k] < t[mn]:
+                        mn = k
+                    elif t[k] > t[mx]:
+                        mx = k
+                t[mx if diff < 0 else mn] -= diff
+        _CUBIC_TABLE = tab.astype(np.int16)
+        _CUBIC_TABLE.setflags(write=False)
+    return _CUBIC_TABLE
+
+
 def _remap(img, mapx, mapy, interpolation=INTER_LINEAR):
     """cv2.remap with BORDER_CONSTANT(0), restating OpenCV's published arithmetic
     (modules/imgproc/src/imgwarp.cpp: ``remap`` converts float maps with ``cvRound(map * INTER_TAB_SIZE)``,
@@ -122,6 +174,7 @@ def _remap(img, mapx, mapy, interpolation=INTER_LINEAR):
     ``cvRound`` of NaN or of an out-of-range double is INT_MIN on x86, a cell far outside the image.  Here the conversion
     to int64 sends NaN / +-inf / beyond-int64 values to INT64_MIN and keeps the others as huge cells, outside the image
     either way; the HIP kernels test for them explicitly (``remap_pixel``); ``oracle/rig_oracle.py`` states the rule.
+    INTER_CUBIC (2) is restated for uint8 images only (``remapBicubic`` with the table of :func:`_cubic_table`).
     cv2 is absent in this environment: parity with cv2.remap
     itself stays unpinned here (reference call: _rigs.py:564-565) -- tests/test_cv2_pins.py pins it wherever cv2 exists."""
     img = np.asarray(img)
@@ -158,8 +211,27 @@ def _remap(img, mapx, mapy, interpolation=INTER_LINEAR):
             out = np.clip(np.rint(acc), info.min, info.max).astype(src.dtype)      # saturate_cast: ties to even
         else:
             out = acc.astype(src.dtype)
+    elif interpolation == INTER_CUBIC:
+        # remapBicubic for uchar: 4 x 4 taps at cell - 1 .. cell + 2 with the 15-bit weights of _cubic_table, taps outside the
+        # image 0, FixedPtCast<int, uchar, 15>: saturate((sum + (1 << 14)) >> 15)
+        if src.dtype != np.uint8:
+            raise NotImplementedError("INTER_CUBIC (2) is available for uint8 images only without OpenCV")
+        with np.errstate(invalid="ignore", over="ignore"):
+            q = np.rint(mapx.astype(np.float64) * 32).astype(np.int64)
+            r = np.rint(mapy.astype(np.float64) * 32).astype(np.int64)
+        wt = _cubic_table()[r & 31, q & 31].astype(np.int64)              # [..., 4, 4]
+        x0, y0 = (q >> 5) - 1, (r >> 5) - 1
+        acc = np.zeros(mapx.shape + (src.shape[2],), np.int64)
+        for k1 in range(4):
+            for k2 in range(4):
+                xx, yy = x0 + k2, y0 + k1
+                ok = (xx >= 0) & (xx < W) & (yy >= 0) & (yy < H)
+                val = np.zeros_like(acc)
+                val[ok] = src[yy[ok], xx[ok]]
+                acc += val * wt[..., k1, k2][..., None]
+        out = np.clip((acc + (1 << 14)) >> 15, 0, 255).astype(np.uint8)
     else:
-        raise NotImplementedError("only INTER_NEAREST (0) and INTER_LINEAR (1) are available without OpenCV")
+        raise NotImplementedError("only INTER_NEAREST (0), INTER_LINEAR (1) and, for uint8, INTER_CUBIC (2) are available without OpenCV")
     return np.ascontiguousarray(out[:, :, 0] if squeeze else out)
 
 

@@ -1,11 +1,18 @@
 """
 active
 ======
-The data-parallel core of ``simplestereo.active`` (reference ``simplestereo/active.py``): the demodulation step of
-Fourier-transform profilometry and the triangulation of its unwrapped phase into a point cloud, each executed by one HIP
-kernel on an AMD MI355X through the C ABI of ``libssamd.so`` (``ssamd_ftp_phase``, ``ssamd_ftp_cloud``, ``include/ssamd.h``).
+Fourier-transform profilometry of ``simplestereo.active`` (reference ``simplestereo/active.py``): ``StereoFTP``, camera
+frame in, point cloud out, and the steps it is made of -- the central stripe, the virtual reference image, the demodulation
+and the triangulation of the unwrapped phase -- each per-pixel step executed by one HIP kernel on an AMD MI355X through the C
+ABI of ``libssamd.so`` (``ssamd_ftp_phase``, ``ssamd_ftp_cloud``: ``include/ssamd.h``; ``ssamd_ftp_reference``,
+``ssamd_stripe_centroids``: ``include/ssamd_active.h``).  No cv2 call anywhere.
 
     import simplestereo_amd as ss
+    ftp = ss.active.StereoFTP(rig, ss.active.buildFringe(period, stripeColor="r"), period)
+    cloud = ftp.getCloud(imgObj)                                        # float64 [H, W, 3], on the device if imgObj is
+
+    stripe = ss.active.findCentralStripe(imgObj, "r", 0.5)              # float64 [H, 2] on the host, or None
+    imgRef = ss.active.ftpReference(fringe, rig, z_plane, roi)          # uint8 [h, w]: the fringe as seen on the plane
     phase = ss.active.ftpPhase(imgObj, imgRef, fc, radius_factor=0.5, unwrap="iir", tau=0.8)
     phase = ss.active.ftpPhase(imgObj, imgRef, fc, unwrap="numpy")      # the reference's default unwrapping
     k = ss.active.ftpFringeOrder(phase, stripe_indexes, rig, z_plane, period, stripeCentralPeak)
@@ -17,17 +24,24 @@ the (virtual) reference image, the per-row band-pass around the carrier ``fc``, 
 ``angle(ghat * conj(g0hat))`` -- optionally followed by the unwrapper the reference passes as ``unwrappingMethod``
 (``unwrap="iir"``) or by what it runs when none is passed, ``np.unwrap`` along x and then along y (``unwrap="numpy"``,
 ``active.py:739-745``).
-It is NOT ``StereoFTP``: building the virtual reference image (``undistort``, ``projectPoints``, ``remap``), finding the
-central stripe and estimating ``fc`` are cv2 calls in the reference and stay with the caller.
+Its inputs come from ``ftpReference`` (the virtual reference image of ``_getProjectorMapping``, ``active.py:459-490``:
+``cv2.projectPoints`` and ``cv2.remap(INTER_CUBIC)`` there, one HIP kernel here) and, for ``fc``, from
+``StereoFTP._calculateCameraFrequency``.
 
 ``ftpCloud`` is the triangulation that ends ``StereoFTP.getCloud`` (``active.py:776-841``, with the projector coordinates
 of ``_getProjectorMapping``, ``:463-485``): ``cv2.projectPoints`` of every pixel centre onto the projector, phase to projector
 column, the epipolar line, ``cv2.undistortPoints``, two rectifying homographies, disparity to depth and the common
 rotation undone -- per pixel, in fp64, in one kernel, so that camera frame -> phase -> unwrapped phase -> cloud stays in HBM.
 ``ftpFringeOrder`` is the one step between the two that needs the central stripe (``active.py:779-788``); ``ftpGeometry``
-packs what both read from the rig.  They are not ``StereoFTP`` either: the virtual reference image (``cv2.remap``),
-``findCentralStripe`` and ``_calculateCameraFrequency`` (which give ``z_plane``, the stripe pixels and ``fc``) stay with the
-caller.
+packs what both read from the rig.
+
+``StereoFTP`` composes them in the reference's order (``active.py:608-841``): ``cv2.undistort`` of the frame (a bilinear
+remap on the maps of ``initUndistortRectifyMap``), ``findCentralStripe`` (per-row centroids by one HIP kernel; only the H
+centroids come to the host), ``_triangulate`` and ``_calculateCameraFrequency`` (O(H) numpy on the host: ``z_plane``,
+``fc``), ``ftpReference``, ``ftpPhase``, ``ftpFringeOrder``, ``ftpCloud``.  Where the reference calls cv2, OpenCV's published
+arithmetic is restated; parity with cv2 itself is pinned only where cv2 is installed (``tests/test_cv2_pins_ftp.py``): the
+bicubic weight table (``_rigs._cubic_table`` lists its choices), ``cv2.undistort``, the float32 roundings of
+``_calculateCameraFrequency``.  ``StereoFTPAnaglyph``, ``StereoFTP_Mapping``, ``StereoFTP_PhaseOnly`` and Gray code are not here.
 
 The band is the reference's, decided exactly (numpy's mask on ``np.fft.fftfreq``); the phase is not bit-identical to
 numpy's pocketfft -- the kernel sums a band-limited direct DFT in another order -- but agrees with the exact angle to a few
@@ -67,17 +81,39 @@ infinity (the reference yields NaN there)
 map; ``stripeCentralPeak`` not a finite number
 =========================================================  =======================
 
-All of them are raised before any native call.  An image or a phase map with no rows or no columns gives an empty array.
+``ftpReference``, ``findCentralStripe`` and ``StereoFTP.getCloud``:
+
+=========================================================  =======================
+condition                                                  exception
+=========================================================  =======================
+the fringe, image or frame neither ndarray nor CUDA/HIP    ``TypeError``
+tensor, or not uint8
+the fringe not [Hp, Wp] or [Hp, Wp, 3], or without pixels  ``ValueError``
+``z_plane`` not a finite number; ``roi`` outside ``res1``  ``ValueError``
+``sensitivity`` outside [0, 1]                             ``ValueError("Threshold must be in the interval [0,1]!")``
+``color`` not 'b', 'g', 'r', 'blue', 'green', 'red'        ``ValueError("Color value not permitted!")``
+the image of ``findCentralStripe`` not [H, W, 3]           ``ValueError``
+fewer than two rows with a stripe (scipy's error)          ``ValueError``
+``interpolation`` other than 'linear' without scipy        ``NotImplementedError``
+a frame that is not 3-D                                    ``ValueError("image must be a BGR color image!")``
+a frame that is not of the rig's ``res1``                  ``ValueError``
+no row of the frame holds a stripe                         ``ValueError("Central stripe not found in image!")``
+``plot=True``                                              ``NotImplementedError``
+=========================================================  =======================
+
+All of them are raised before any native call.  An image or a phase map with no rows or no columns gives an empty array;
+``findCentralStripe`` of such an image is ``None``.
 """
 import numbers
 
 import numpy as np
 
 from . import _native
-from ._rigs import _dist_vector
+from ._rigs import INTER_LINEAR, _dist_vector, _distort, _init_undistort_rectify_map, _remap, _undistort_points
 from ._native import c_double as _c_double, is_device_tensor as _is_device_tensor
 
-__all__ = ["ftpPhase", "ftpCloud", "ftpFringeOrder", "ftpGeometry", "FtpGeometry", "MAX_WIDTH"]
+__all__ = ["ftpPhase", "ftpCloud", "ftpFringeOrder", "ftpGeometry", "FtpGeometry", "MAX_WIDTH", "ftpReference",
+           "findCentralStripe", "buildFringe", "StereoFTP"]
 
 MAX_WIDTH = 8192          # SSAMD_FTP_MAX_W: twiddle table, gray rows and a chunk of bins of one row in 160 KiB of LDS
 
@@ -138,8 +174,8 @@ def ftpPhase(imgObj, imgRef, fc, radius_factor=0.5, unwrap=None, tau=1):
     The demodulation of the reference's ``StereoFTP.getCloud`` (``active.py:675-737``): for every image row, the spectrum
     of the object image and of the reference image is cut to the band ``[fc - radius_factor*fc, fc + radius_factor*fc]``
     (bins of ``np.fft.fftfreq(W)``, bounds included), transformed back, and the phase is
-    ``angle(ghat * conj(g0hat))``.  It is not ``StereoFTP``: the reference image, ``fc`` and the triangulation of the
-    phase are the caller's.
+    ``angle(ghat * conj(g0hat))``.  It is not ``StereoFTP`` but one step of :class:`StereoFTP`: called on its own, the
+    reference image is :func:`ftpReference`'s and ``fc`` and the triangulation of the phase are the caller's.
 
     Parameters
     ----------
@@ -342,8 +378,8 @@ def ftpFringeOrder(phaseUnwrapped, stripe_indexes, rig, z_plane=None, period=Non
 
     With ``theta`` the phase at the stripe pixels and ``u_A`` the projector column of those pixels on the reference plane,
     ``k = ceil(mean((stripeCentralPeak - u_A) * fp - theta / (2 * pi)) - 0.5)``: the mean rounded to the nearest integer,
-    a half rounded down.  It is not ``StereoFTP``: finding the stripe (``findCentralStripe``), ``z_plane`` and
-    ``stripeCentralPeak`` stay with the caller.
+    a half rounded down.  A step of :class:`StereoFTP`; on its own, the stripe is :func:`findCentralStripe`'s and ``z_plane``
+    and ``stripeCentralPeak`` are the caller's.
 
     Parameters
     ----------
@@ -393,8 +429,8 @@ def ftpCloud(phaseUnwrapped, rig, z_plane=None, period=None, k=0, roi=None):
     ``z_plane * R.dot(inv(K1))`` as the 3x3 rotation, ``active.py:463-485``), the projector column moved by
     ``(phase + 2 k pi) / (2 pi fp)``, the row on the epipolar line, ``cv2.undistortPoints`` with ``P = K2`` (five
     iterations), the two rectifying homographies, ``baseline / |disparity|`` and the common rotation undone.  One HIP kernel,
-    fp64 throughout (``ftp_cloud_kernel``).  It is not ``StereoFTP``: the phase, ``z_plane`` and ``k`` are the caller's
-    (``ftpPhase``, ``ftpFringeOrder``).  Not bit-identical to cv2 (another operation order).
+    fp64 throughout (``ftp_cloud_kernel``).  A step of :class:`StereoFTP`; on its own, the phase and ``k`` come from
+    ``ftpPhase`` and ``ftpFringeOrder`` and ``z_plane`` is the caller's.  Not bit-identical to cv2 (another operation order).
 
     Parameters
     ----------
@@ -428,3 +464,399 @@ def ftpCloud(phaseUnwrapped, rig, z_plane=None, period=None, k=0, roi=None):
         if phase.data_ptr() % 16:
             phase = phase.clone()     # a view at an odd storage offset: the kernel reads two phases per 16-byte load
     return _native.run("ssamd_ftp_cloud", (phase,), (h, w, 3), lambda src, out: (src, h, w, x0, y0, G.geom.ctypes.data, order, out), _INVALID)
+
+
+# ------------------------------------------------------------------------------------------------ the front end: StereoFTP
+def _getCentralPeak(length, period, shift=0):
+    """Column of the brightest pixel of the central stripe of a :func:`buildFringe` fringe (``active.py:67-84``)."""
+    k = (length / 2) // period
+    return period * (k - shift / (2 * np.pi))
+
+
+_STRIPE_CHANNEL = {"b": 0, "blue": 0, "g": 1, "green": 1, "r": 2, "red": 2}
+
+
+def buildFringe(period, shift=0, dims=(1280, 720), vertical=False, stripeColor=None, dtype=np.uint8):
+    """
+    Build a sinusoidal fringe image (the reference's ``buildFringe``, ``active.py:87-148``, the same formulas bit for bit).
+
+    Parameters
+    ----------
+    period : float
+        Fringe period along the x axis, in pixels.
+    shift : float, optional
+        Shift of the cosine's argument, in pixels.  Default 0.
+    dims : tuple, optional
+        Image dimensions as (width, height).  Default (1280, 720).
+    vertical : bool, optional
+        Build the fringe along the vertical.  Default False.
+    stripeColor : str, optional
+        'blue', 'green', 'red' (or 'b', 'g', 'r'): the central period keeps that channel only, and the image is BGR.
+        Default None: a gray image without stripe.
+    dtype : numpy.dtype, optional
+        An integer type scales the fringe to its maximum.  Default ``np.uint8``.
+
+    Returns
+    -------
+    numpy.ndarray
+        ``[height, width]``, or ``[height, width, 3]`` with a stripe.
+    """
+    if vertical is True:
+        dims = (dims[1], dims[0])
+    row = ((1 + np.cos(2 * np.pi * (1 / period) * (np.arange(dims[0], dtype=float) + shift))) / 2)[np.newaxis, :]
+    if np.dtype(dtype).char in np.typecodes["AllInteger"]:
+        row *= np.iinfo(dtype).max
+    if stripeColor is not None:
+        if stripeColor not in _STRIPE_CHANNEL:
+            raise ValueError("stripeColor value not permitted!")
+        row = np.repeat(row[:, :, np.newaxis], 3, axis=2)
+        peak = _getCentralPeak(dims[0], period, shift)
+        left = int(peak - period / 2)
+        right = int(left + period)
+        keep = _STRIPE_CHANNEL[stripeColor]
+        for ch in range(3):
+            if ch != keep:
+                row[0, left:right, ch] = 0
+    full = np.repeat(row.astype(dtype), dims[1], axis=0)
+    if vertical is True:
+        full = np.rot90(full, k=3, axes=(0, 1))
+    return full
+
+
+def _gray(img):
+    """``StereoFTP.convertGrayscale`` of a checked image: the channel maximum of BGR, a gray image as it is"""
+    if img.ndim == 2:
+        return img
+    return img.amax(dim=2) if _is_device_tensor(img) else np.max(img, axis=2)
+
+
+def ftpReference(fringe, rig, z_plane=None, roi=None, period=None):
+    """
+    Virtual reference image: the fringe as the camera would see it on the reference plane at ``z_plane``.
+
+    The integer-grid half of the reference's ``StereoFTP._getProjectorMapping`` (``active.py:459-490``): for every camera
+    pixel ``(x, y)`` of the roi -- integer coordinates, no ``+ 0.5`` -- ``cv2.projectPoints`` onto the projector with
+    ``z_plane * R.dot(inv(K1))`` as the 3x3 rotation (the operations of ``ftpCloud``, fp64), the two coordinates rounded to
+    float32, and ``cv2.remap(fringe, mapx, mapy, INTER_CUBIC)`` with a constant border 0 in OpenCV's published 8-bit
+    arithmetic: 1/32-pixel fractions, 4 x 4 taps with the 15-bit integer weights of ``initInterTab2D`` (restated in
+    ``_rigs._cubic_table``, where every choice is listed), ``clip((sum + (1 << 14)) >> 15, 0, 255)``.  Pixels whose map
+    coordinates are not finite, or lie wholly outside the fringe, are 0.  One HIP kernel (``ftp_reference_kernel``); equal
+    byte for byte to ``_rigs._remap(fringe, mapx, mapy, INTER_CUBIC)`` on the maps of the numpy restatement.  Parity with
+    cv2 itself is not pinned.
+
+    Parameters
+    ----------
+    fringe : ndarray or CUDA/HIP tensor, uint8
+        ``[Hp, Wp]`` gray or ``[Hp, Wp, 3]`` BGR (reduced by the channel maximum, ``convertGrayscale``), at least one pixel.
+    rig : StereoRig
+        Camera in position 1, projector in position 2 -- or an :func:`ftpGeometry` result, with ``z_plane`` and ``roi`` left
+        ``None``.
+    z_plane : float
+        Distance of the reference plane from the camera.
+    roi : (x, y, width, height), optional
+        Region of the camera image to build.  Default: the whole ``rig.res1``.
+    period : optional
+        Not read (the reference image does not depend on it); accepted so that the arguments of ``ftpCloud`` can be passed.
+
+    Returns
+    -------
+    ndarray or tensor
+        uint8 ``[height, width]``: a new array, or a tensor on the fringe's device computed on its current stream.
+    """
+    if isinstance(rig, FtpGeometry):
+        if z_plane is not None or roi is not None:
+            raise ValueError("with a packed geometry in place of the rig, z_plane and roi are the geometry's: pass None")
+        G = rig
+    else:
+        G = ftpGeometry(rig, z_plane, 1.0, roi)
+    fr, hp, wp, _ = _image(fringe, "fringe")
+    if hp == 0 or wp == 0:
+        raise ValueError("fringe must have at least one pixel")
+    fr = _gray(fr)
+    x0, y0, w, h = G.roi
+    return _native.run("ssamd_ftp_reference", (fr,), (h, w),
+                       lambda src, out: (src, hp, wp, h, w, x0, y0, G.geom.ctypes.data, out), _INVALID, dtype=np.uint8)
+
+
+def _fill_linear(y, x):
+    """``scipy.interpolate.interp1d(y[valid], x[valid], kind="linear", fill_value="extrapolate")(y)`` in numpy, scipy's own
+    formula (``interp1d._call_linear``): every row -- the valid ones too -- is ``slope * (y - y_lo) + x_lo`` on the pair of
+    knots around it (the first or last pair outside them), so a valid row may differ from its centroid in the last bit."""
+    valid = ~np.isnan(x)
+    ky, kx = y[valid], x[valid]
+    if ky.size < 2:
+        raise ValueError("x and y arrays must have at least 2 entries")          # scipy's message
+    hi = np.searchsorted(ky, y).clip(1, ky.size - 1).astype(int)
+    lo = hi - 1
+    slope = (kx[hi] - kx[lo]) / (ky[hi] - ky[lo])
+    return slope * (y - ky[lo]) + kx[lo]
+
+
+def findCentralStripe(image, color="r", sensitivity=0.5, interpolation="linear"):
+    """
+    Find the coordinates of a coloured vertical stripe in the image, with subpixel accuracy along x (the reference's
+    ``findCentralStripe``, ``active.py:272-345``).
+
+    Per row, the chosen channel is zeroed where ``value < 255 * sensitivity`` and the centroid ``sum(v * x) / sum(v)`` is
+    taken: one HIP kernel (``stripe_centroid_kernel``), exact integer sums and one fp64 division, numpy's result bit for
+    bit; only the H centroids come to the host.  Rows without stripe are filled by linear interpolation over the rows,
+    extrapolated at both ends: scipy's ``interp1d`` formula restated in numpy (``_fill_linear``), bit for bit.
+
+    Parameters
+    ----------
+    image : ndarray or CUDA/HIP tensor, uint8 ``[H, W, 3]``
+        BGR image with a coloured vertical stripe.
+    color : str, optional
+        'blue', 'green' or 'red' (or 'b', 'g', 'r').  Default 'r'.
+    sensitivity : float, optional
+        Sensitivity of the colour match in [0, 1].  Default 0.5.
+    interpolation : str, optional
+        ``kind`` of ``scipy.interpolate.interp1d``.  ``'linear'`` needs no scipy; any other kind is handed to scipy and is
+        ``NotImplementedError`` where scipy is not installed.
+
+    Returns
+    -------
+    numpy.ndarray or None
+        float64 ``[H, 2]``: (x, y) of the stripe centre in every row (y = row + 0.5), on the host; ``None`` when no row
+        holds a stripe.
+    """
+    if not (sensitivity >= 0 and sensitivity <= 1):
+        raise ValueError("Threshold must be in the interval [0,1]!")
+    img, h, w, ch = _image(image, "image")
+    if ch != 3:
+        raise ValueError("image must be [H, W, 3] (BGR)")
+    if not isinstance(color, str) or color not in _STRIPE_CHANNEL:
+        raise ValueError("Color value not permitted!")
+    # uint8 < fp64 product (active.py:319-320) <=> uint8 < ceil(product): the integer threshold the kernel compares with
+    threshold = int(np.ceil(255 * float(sensitivity)))
+    if w == 0:
+        return None
+    x = _native.run("ssamd_stripe_centroids", (img,), (h,),
+                    lambda src, out: (src, h, w, _STRIPE_CHANNEL[color], threshold, out), _INVALID)
+    if _is_device_tensor(x):
+        x = x.cpu().numpy()
+    if np.isnan(x).all():
+        return None
+    y = np.arange(0.5, h, 1)
+    if interpolation == "linear":
+        x = _fill_linear(y, x)
+    else:
+        try:
+            from scipy.interpolate import interp1d
+        except ImportError:
+            raise NotImplementedError("interpolation=%r needs scipy, which is not installed: only 'linear' is built in"
+                                      % (interpolation,)) from None
+        valid = ~np.isnan(x)
+        x = interp1d(y[valid], x[valid], kind=interpolation, fill_value="extrapolate")(y)
+    return np.vstack((x, y)).T
+
+
+def _project_points(P, R, T, K, dist):
+    """``cv2.projectPoints(P [n, 3], R (3x3), T, K, dist)`` -> [n, 2], the published camera model in fp64 numpy"""
+    X = P.dot(np.asarray(R, dtype=np.float64).T) + np.asarray(T, dtype=np.float64).reshape(1, 3)
+    xd, yd = _distort(X[:, 0] / X[:, 2], X[:, 1] / X[:, 2], _dist_vector(dist))
+    return np.stack([K[0, 0] * xd + K[0, 2], K[1, 1] * yd + K[1, 2]], axis=1)
+
+
+def _perspective(pts, H):
+    """``cv2.perspectiveTransform`` of [n, 2] points with a 3x3 matrix"""
+    q = np.hstack((pts, np.ones((pts.shape[0], 1)))).dot(H.T)
+    return q[:, :2] / q[:, 2:]
+
+
+class StereoFTP:
+    """
+    Manager of the Stereo Fourier Transform Profilometry (the reference's ``StereoFTP``, ``active.py:351-841``): camera
+    frame in, point cloud out, with no cv2 call.
+
+    Parameters
+    ----------
+    stereoRig : StereoRig
+        Camera in position 1 (world origin), projector in position 2.
+    fringe : numpy.ndarray
+        BGR image projected by the projector (:func:`buildFringe` with a ``stripeColor``), uint8.
+    period : float
+        Period of the fringe, in pixels.
+    shift : float, optional
+        Shift used to build the fringe.  Default 0.
+    stripeColor : str, optional
+        Colour of the central stripe: 'blue', 'green', 'red' or 'b', 'g', 'r'.  Default 'red'.
+    stripeSensitivity : float, optional
+        Sensitivity to find the stripe, see :func:`findCentralStripe`.  Default 0.5.
+
+    The attributes are the reference's: ``fringe`` (gray), ``fringeDims``, ``fp``, ``stripeCentralPeak``, ``F``,
+    ``Rectify1``, ``Rectify2``, ``ep``, ``R_inv``.  The gray fringe and the undistortion maps of the camera go to a device
+    once per instance, the bicubic weight table once per device.
+    """
+
+    def __init__(self, stereoRig, fringe, period, shift=0, stripeColor="red", stripeSensitivity=0.5):
+        self.stereoRig = stereoRig
+        self.fringe = self.convertGrayscale(fringe)
+        self.fringeDims = fringe.shape[:2][::-1]
+        self.period = period
+        self.fp = 1 / period
+        self.stripeColor = stripeColor
+        self.stripeSensitivity = stripeSensitivity
+        self.stripeCentralPeak = _getCentralPeak(self.fringeDims[0], period, shift)
+        self.F = self.stereoRig.getFundamentalMatrix()
+        self.Rectify1, self.Rectify2, commonR = _low_level_rectify(stereoRig)
+        ep = self.stereoRig.intrinsic2.dot(self.stereoRig.T)
+        self.ep = ep / ep[2]
+        R_inv = np.linalg.inv(commonR)
+        R_inv = np.hstack((np.vstack((R_inv, np.zeros((1, 3)))), np.zeros((4, 1))))
+        R_inv[3, 3] = 1
+        self.R_inv = R_inv
+        self._undistort_maps = None      # float32 (mapx, mapy) of cv2.undistort, host
+        self._on_device = {}             # device -> (gray fringe, mapx, mapy) tensors
+
+    @staticmethod
+    def convertGrayscale(img):
+        """Grayscale by the channel maximum: the stripe (0, 0, 255) becomes white, which the FFT needs."""
+        return np.max(img, axis=2)
+
+    def _device_state(self, device):
+        import torch
+        if str(device) not in self._on_device:
+            mx, my = self._host_maps()
+            self._on_device[str(device)] = (torch.from_numpy(np.ascontiguousarray(self.fringe)).to(device),
+                                            torch.from_numpy(mx).to(device), torch.from_numpy(my).to(device))
+        return self._on_device[str(device)]
+
+    def _host_maps(self):
+        if self._undistort_maps is None:
+            rig = self.stereoRig
+            self._undistort_maps = _init_undistort_rectify_map(rig.intrinsic1, rig.distCoeffs1, np.eye(3), rig.intrinsic1, rig.res1)
+        return self._undistort_maps
+
+    def _undistort(self, img):
+        """``cv2.undistort(img, K1, distCoeffs1)``: the float32 maps of ``initUndistortRectifyMap(K1, D1, I, K1, res1)`` and a
+        bilinear remap with a constant border 0 -- ``remap_bgr_kernel`` on a device frame, ``_rigs._remap`` on a host frame
+        (the same bytes).  Parity with cv2 is not pinned."""
+        if not _is_device_tensor(img):
+            mx, my = self._host_maps()
+            return _remap(img, mx, my, INTER_LINEAR)
+        import torch
+        _, dmx, dmy = self._device_state(img.device)
+        h, w = int(dmx.shape[0]), int(dmx.shape[1])
+        out = torch.empty((h, w, 3), dtype=torch.uint8, device=img.device)
+        _native.call_on_stream(img, _native.lib().ssamd_remap_bgr_device, img.data_ptr(), int(img.shape[0]), int(img.shape[1]),
+                               dmx.data_ptr(), dmy.data_ptr(), h, w, INTER_LINEAR, out.data_ptr())
+        return out
+
+    def _triangulate(self, camPoints, p_x, roi):
+        """
+        For each undistorted camera point and the projector column ``p_x`` it corresponds to, the 3-D point
+        (``active.py:561-605``), O(n) numpy on the host: the projector row from the epipolar line of ``F``, the camera point
+        through ``Rectify1``, the projector point through ``cv2.undistortPoints(P=K2)`` (``_rigs._undistort_points``) and
+        ``Rectify2``, ``baseline / |disparity|`` and the common rotation undone.  fp64 throughout, as the reference is for
+        its float64 stripe; ``camPoints`` is not modified (the reference adds the roi offset in place).  Parity with cv2 is
+        not pinned.
+        """
+        rig = self.stereoRig
+        cam = np.array(camPoints, dtype=np.float64).reshape(-1, 2)
+        n = cam.shape[0]
+        cam[:, 0] += roi[0]
+        cam[:, 1] += roi[1]
+        lines = np.hstack((cam, np.ones((n, 1)))).dot(self.F.T)
+        p_x = np.full((n,), p_x, dtype=np.float64) if np.isscalar(p_x) else np.asarray(p_x, dtype=np.float64).flatten()
+        p_y = -(lines[:, 0] * p_x + lines[:, 2]) / lines[:, 1]
+        pc = _perspective(cam, self.Rectify1)
+        pp = _undistort_points(np.stack([p_x, p_y], axis=1), rig.intrinsic2, rig.distCoeffs2, R=rig.intrinsic2)
+        pp = _perspective(pp, self.Rectify2)
+        disparity = np.abs(pp[:, [0]] - pc[:, [0]])
+        pw = rig.getBaseline() * (np.hstack((pc, np.ones((n, 1)))) / disparity)
+        return pw.dot(np.ascontiguousarray(self.R_inv[:3, :3]).T)
+
+    def _calculateCameraFrequency(self, objPoints):
+        """
+        Carrier frequency on the camera of each object point (``active.py:495-559``), O(n) numpy on the host: the point on
+        the projector, two points half a period to either side, back to the plane at the point's depth, onto the camera;
+        ``1 / Tc`` with ``Tc`` from the first Euclid theorem.  The reference's dtypes are kept where they are observable:
+        ``objPoints`` is cast to float32, and because cv2 returns float32 for float32 input, ``pCenter``
+        (``cv2.projectPoints``) and the undistorted points (``cv2.undistortPoints``) are computed in fp64 and rounded to
+        float32 at those two places.  Parity with cv2 is not pinned.
+        """
+        rig = self.stereoRig
+        Ac, Ap = np.asarray(rig.intrinsic1, dtype=np.float64), np.asarray(rig.intrinsic2, dtype=np.float64)
+        R, T = np.asarray(rig.R, dtype=np.float64), np.asarray(rig.T, dtype=np.float64)
+        Op = (-np.linalg.inv(R).dot(T)).flatten()
+        obj = np.asarray(objPoints).reshape(-1, 3).astype(np.float32)
+        n = obj.shape[0]
+        pCenter = _project_points(obj.astype(np.float64), R, T, Ap, rig.distCoeffs2).astype(np.float32)
+        half = np.float32((1 / self.fp) / 2)
+        points = np.vstack((np.stack([pCenter[:, 0] - half, pCenter[:, 1]], axis=1),
+                            np.stack([pCenter[:, 0] + half, pCenter[:, 1]], axis=1)))
+        und = _undistort_points(points.astype(np.float64), Ap, rig.distCoeffs2, R=Ap).astype(np.float32)
+        pp = np.hstack((und, np.ones((2 * n, 1), dtype=np.float32)))
+        z = np.tile(obj[:, 2].reshape(-1, 1), (2, 1))
+        hh = np.linalg.inv(Ap.dot(R)).dot(pp.T).T
+        s = (z - Op[2]) / hh[:, [2]]
+        pw = s * hh + Op.reshape(1, 3)
+        pc = _project_points(pw, np.eye(3), np.zeros(3), Ac, rig.distCoeffs1)
+        a, b = pc[:n], pc[n:]
+        Tc = ((a[:, 0] - b[:, 0]) ** 2 + (a[:, 1] - b[:, 1]) ** 2) / np.abs(a[:, 0] - b[:, 0])
+        return 1 / Tc
+
+    def _frame(self, imgObj, roi):
+        """The checks and the first four steps of ``getCloud``: -> (undistorted roi cut, roi, stripe, stripe_indexes)"""
+        if not (_is_device_tensor(imgObj) or isinstance(imgObj, np.ndarray)):
+            raise TypeError("imgObj must be a uint8 ndarray or a CUDA/HIP torch.uint8 tensor")
+        if imgObj.ndim != 3:
+            raise ValueError("image must be a BGR color image!")
+        img, h, w, _ = _image(imgObj, "imgObj")
+        widthC, heightC = (int(v) for v in self.stereoRig.res1)
+        if (w, h) != (widthC, heightC):
+            raise ValueError("imgObj is %d x %d but the camera resolution is %d x %d (width x height)" % (w, h, widthC, heightC))
+        box = _roi(roi, self.stereoRig.res1)
+        cut = self._undistort(img)[box[1]:box[1] + box[3], box[0]:box[0] + box[2]]
+        stripe = findCentralStripe(cut, self.stripeColor, self.stripeSensitivity)
+        if stripe is None:
+            raise ValueError("Central stripe not found in image!")
+        return cut, box, stripe, np.ceil(stripe - 0.5).astype(np.int64)
+
+    def getCloud(self, imgObj, radius_factor=0.5, roi=None, unwrappingMethod=None, plot=False):
+        """
+        Process a camera frame and get the point cloud (``active.py:608-841``).
+
+        The reference's steps in its order: ``cv2.undistort`` of the frame (bilinear remap on the maps of
+        ``initUndistortRectifyMap(K1, D1, I, K1)``), the roi cut, :func:`findCentralStripe`, the stripe's pixel indexes,
+        ``_triangulate`` of the stripe -> ``z_plane`` (its mean depth), ``_calculateCameraFrequency`` -> ``fc``,
+        :func:`ftpReference`, :func:`ftpPhase`, :func:`ftpFringeOrder`, :func:`ftpCloud`.  With a device tensor the frame,
+        the reference image, the phase and the cloud stay on the device: what crosses to the host are the H stripe
+        centroids and the H phase values at the stripe.
+
+        Parameters
+        ----------
+        imgObj : ndarray or CUDA/HIP tensor, uint8 ``[H, W, 3]``
+            BGR frame of the camera, of the rig's ``res1``.
+        radius_factor : float, optional
+            Radius factor of the pass band.  Default 0.5.
+        roi : (x, y, width, height), optional
+            Region of interest.  Default None: the whole frame.
+        unwrappingMethod : callable, optional
+            Takes the wrapped phase (an array or tensor like the frame) and returns it unwrapped, e.g.
+            ``ss.unwrapping.infiniteImpulseResponse``.  Default None: ``np.unwrap`` along x, then y (``unwrap="numpy"``).
+        plot : bool, optional
+            ``True`` is ``NotImplementedError``: there is no display here.
+
+        Returns
+        -------
+        ndarray or tensor
+            float64 ``[height, width, 3]`` of the frame or the roi: an ndarray for a host frame, a tensor on the frame's
+            device for a device frame.
+        """
+        if plot:
+            raise NotImplementedError("plot=True needs cv2 windows and matplotlib, which this package does not use")
+        cut, box, stripe, stripe_indexes = self._frame(imgObj, roi)
+        stripe_world = self._triangulate(stripe, self.stripeCentralPeak, box)
+        z_plane = np.mean(stripe_world[:, 2])
+        fc = self._calculateCameraFrequency(stripe_world)
+        G = ftpGeometry(self.stereoRig, z_plane, self.period, box)
+        fringe = self._device_state(cut.device)[0] if _is_device_tensor(cut) else self.fringe
+        imgRef = ftpReference(fringe, G)
+        if unwrappingMethod is None:
+            phase = ftpPhase(cut, imgRef, fc, radius_factor, unwrap="numpy")
+        else:
+            phase = unwrappingMethod(ftpPhase(cut, imgRef, fc, radius_factor))
+        k = ftpFringeOrder(phase, stripe_indexes, G, stripeCentralPeak=self.stripeCentralPeak)
+        return ftpCloud(phase, G, k=k)

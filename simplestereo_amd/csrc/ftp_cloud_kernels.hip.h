@@ -34,14 +34,15 @@ static_assert(sizeof(FtpCloudGeom) == 68 * sizeof(double), "SSAMD_FTP_CLOUD_NGEO
 constexpr int FTP_CLOUD_THREADS = 256;
 constexpr int FTP_CLOUD_WAVES = FTP_CLOUD_THREADS / 64;
 
-// One pixel centre (u, v) and its unwrapped phase (already shifted by the fringe order) -> point o[0..2].
-template <int MODEL>
-__device__ __forceinline__ void ftp_cloud_pixel(const FtpCloudGeom &G, double u, double v, double ph, double *o)
+// cv2.projectPoints((u, v, 1), M, T, K2, distCoeffs2) with the 3x3 M copied into the rotation matrix (active.py:478-481):
+// the operations of tests/_ftp_cloud_ref.py (project_points) in that order.  Geom is any struct that begins like FtpCloudGeom
+// (M, T, f2, d): ftp_cloud_kernel and ftp_reference_kernel (ftp_reference_kernels.hip.h) share this text.
+template <int MODEL, class Geom>
+__device__ __forceinline__ void ftp_project(const Geom &G, double u, double v, double &Xa, double &Ya)
 {
 #pragma clang fp contract(off)
     const double k1 = G.d[0], k2 = G.d[1], p1 = G.d[2], p2 = G.d[3], k3 = G.d[4], k4 = G.d[5], k5 = G.d[6], k6 = G.d[7];
     const double s1 = G.d[8], s2 = G.d[9], s3 = G.d[10], s4 = G.d[11];
-    // projector coordinates of the camera pixel on the reference plane: projectPoints
     const double X = ((G.M[0] * u + G.M[1] * v) + G.M[2]) + G.T[0];
     const double Y = ((G.M[3] * u + G.M[4] * v) + G.M[5]) + G.T[1];
     const double Z = ((G.M[6] * u + G.M[7] * v) + G.M[8]) + G.T[2];
@@ -59,7 +60,20 @@ __device__ __forceinline__ void ftp_cloud_pixel(const FtpCloudGeom &G, double u,
             yd = (yd + s3 * r2) + s4 * r4;
         }
     }
-    const double Xa = G.f2[0] * xd + G.f2[2], Ya = G.f2[1] * yd + G.f2[3];
+    Xa = G.f2[0] * xd + G.f2[2];
+    Ya = G.f2[1] * yd + G.f2[3];
+}
+
+// One pixel centre (u, v) and its unwrapped phase (already shifted by the fringe order) -> point o[0..2].
+template <int MODEL>
+__device__ __forceinline__ void ftp_cloud_pixel(const FtpCloudGeom &G, double u, double v, double ph, double *o)
+{
+#pragma clang fp contract(off)
+    const double k1 = G.d[0], k2 = G.d[1], p1 = G.d[2], p2 = G.d[3], k3 = G.d[4], k4 = G.d[5], k5 = G.d[6], k6 = G.d[7];
+    const double s1 = G.d[8], s2 = G.d[9], s3 = G.d[10], s4 = G.d[11];
+    // projector coordinates of the camera pixel on the reference plane: projectPoints
+    double Xa, Ya;
+    ftp_project<MODEL>(G, u, v, Xa, Ya);
     // phase -> projector column, row on the epipolar line
     const double Xh = Xa + ph / G.two_pi_fp;
     const double Yh = ((Xh - G.ep[0]) / (Xa - G.ep[0])) * (Ya - G.ep[1]) + G.ep[1];

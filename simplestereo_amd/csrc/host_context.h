@@ -149,6 +149,8 @@ struct Ctx {
     DevBuf uwIn, uwOut;                 // host-buffer phase unwrapping (unwrap_kernels.hip.h)
     DevBuf ftpBand, ftpPhase;           // FTP phase (ftp_kernels.hip.h): kept bins per row; the wrapped map on its way to the unwrapper
     std::map<int, DevBuf> ftpTabs;      // twiddle table e^{2 pi i j / w} per width, built on the device
+    DevBuf ftpRefTab;                   // FTP reference image (ftp_reference_kernels.hip.h): the bicubic weight table, uploaded once
+    bool ftpRefTabReady = false;
     int32_t *ftpBandHost = nullptr;     // pinned staging of the bands: the asynchronous upload reads it after the call returned
     size_t ftpBandHostCap = 0;          // ... in int32 pairs
     hipEvent_t ftp_band_copied = nullptr;   // recorded behind that upload; the next call waits for it before it refills the staging

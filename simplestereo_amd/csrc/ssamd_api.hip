@@ -1,4 +1,4 @@
-// libssamd.so: host side of the C ABI declared in include/ssamd.h (gfx950 / ROCm).
+// libssamd.so: host side of the C ABI declared in include/ssamd.h and include/ssamd_active.h (gfx950 / ROCm).
 // Owns device scratch, chooses launch geometry, launches the HIP kernels.
 // There is deliberately no CPU code path for the operators of this library.
 // This file is the main translation unit and the map of the host side: the kernel headers, then the host sections (host_*.h), which it
@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/ssamd.h"
+#include "../../include/ssamd_active.h"
 #include "asw_shared.hip.h"
 #include "asw_kernels.hip.h"
 #include "asw_pipe_kernel.hip.h"
@@ -45,6 +46,7 @@ namespace ssamd {
 #include "np_unwrap_kernels.hip.h"
 #include "ftp_kernels.hip.h"
 #include "ftp_cloud_kernels.hip.h"
+#include "ftp_reference_kernels.hip.h"
 
 using namespace ssamd;
 
@@ -60,5 +62,7 @@ using namespace ssamd;
 #include "host_np_unwrap.h"     // np.unwrap
 #include "host_ftp_phase.h"     // FTP phase
 #include "host_ftp_cloud.h"     // FTP cloud
+#include "host_ftp_reference.h" // FTP virtual reference image (include/ssamd_active.h)
+#include "host_stripe.h"        // FTP central stripe centroids (include/ssamd_active.h)
 #include "host_library.h"       // version, last error, device count, kernel names, options, counters, autotune switch, geometry queries, profile
 #include "host_debug.h"         // verification entry points (ssamd_bgr2lab, ssamd_debug_*) and debug_libm_kernel

@@ -1,0 +1,361 @@
+"""The front end of the reference's StereoFTP.getCloud (active.py:272-345, :432-605, :631-673) restated in plain numpy: the
+bicubic remap of 8-bit images and its weight table, the projector map and the virtual reference image, the central stripe's
+centroids and their fill, _triangulate and _calculateCameraFrequency, buildFringe -- and with tests/_ftp_ref.py and
+tests/_ftp_cloud_ref.py the whole pipeline, camera frame to cloud.  Where the reference calls cv2 the published OpenCV
+arithmetic is written out.  A renderer makes the camera frames: a plane with a smooth bump, lit by the fringe through a rig.
+
+Nothing here imports simplestereo_amd."""
+import json
+import os
+
+import numpy as np
+
+import _ftp_cloud_ref as C
+import _ftp_ref as P
+
+CHANNEL = {"b": 0, "blue": 0, "g": 1, "green": 1, "r": 2, "red": 2}
+
+
+# ------------------------------------------------------------------------------------------------ cv2.remap, 8-bit
+def cubic_table():
+    """initInterTab2D(INTER_CUBIC, fixpt): int64 [32 fy, 32 fx, 4 tap rows, 4 tap columns].  float32 coefficients with
+    A = -0.75 at i / 32, the float32 outer product times 32768 rounded half to even and saturated to short (1.0 -> 32767), then the
+    difference to 32768 taken from one tap among (2..3, 2..3): the largest when the sum is short, the smallest when it is over,
+    scanned from (2, 2) with "smaller than the minimum" tested first."""
+    f = np.float32
+    A = f(-0.75)
+    x = np.arange(32, dtype=np.float32) * f(1.0 / 32)
+    c = np.empty((32, 4), np.float32)
+    c[:, 0] = ((A * (x + f(1)) - f(5) * A) * (x + f(1)) + f(8) * A) * (x + f(1)) - f(4) * A
+    c[:, 1] = ((A + f(2)) * x - (A + f(3))) * x * x + f(1)
+    c[:, 2] = ((A + f(2)) * (f(1) - x) - (A + f(3))) * (f(1) - x) * (f(1) - x) + f(1)
+    c[:, 3] = f(1) - c[:, 0] - c[:, 1] - c[:, 2]
+    tab = np.empty((32, 32, 4, 4), np.int64)
+    for i in range(32):
+        for j in range(32):
+            t = np.clip(np.rint(np.outer(c[i], c[j]) * f(32768)).astype(np.int64), -32768, 32767)
+            diff = int(t.sum()) - 32768
+            if diff:
+                mn = mx = (2, 2)
+                for k in ((2, 2), (2, 3), (3, 2), (3, 3)):
+                    if t[k] < t[mn]:
+                        mn = k
+                    elif t[k] > t[mx]:
+                        mx = k
+                t[mx if diff < 0 else mn] -= diff
+            tab[i, j] = t
+    return tab
+
+
+_TABLE = []
+
+
+def _q32(m):
+    """rint(map * 32) as int64; NaN, +-inf and products outside int32 -> a cell far outside every image"""
+    with np.errstate(invalid="ignore", over="ignore"):
+        v = np.asarray(m, dtype=np.float32).astype(np.float64) * 32
+        bad = ~(np.abs(v) < 2.0 ** 31)
+        return np.where(bad, -(1 << 40), np.rint(np.where(bad, 0, v))).astype(np.int64)
+
+
+def remap_cubic(img, mapx, mapy):
+    """cv2.remap(img [H, W] uint8, mapx, mapy float32, INTER_CUBIC, BORDER_CONSTANT 0)"""
+    if not _TABLE:
+        _TABLE.append(cubic_table())
+    H, W = img.shape
+    q, r = _q32(mapx), _q32(mapy)
+    wt = _TABLE[0][r & 31, q & 31]
+    x0, y0 = (q >> 5) - 1, (r >> 5) - 1
+    acc = np.zeros(q.shape, np.int64)
+    for k1 in range(4):
+        for k2 in range(4):
+            xx, yy = x0 + k2, y0 + k1
+            ok = (xx >= 0) & (xx < W) & (yy >= 0) & (yy < H)
+            val = np.zeros(q.shape, np.int64)
+            val[ok] = img[yy[ok], xx[ok]]
+            acc += val * wt[..., k1, k2]
+    return np.clip((acc + (1 << 14)) >> 15, 0, 255).astype(np.uint8)
+
+
+def remap_linear(img, mapx, mapy):
+    """cv2.remap(img [H, W, 3] uint8, ..., INTER_LINEAR, BORDER_CONSTANT 0): 1/32-pixel fractions, (S + 512) >> 10"""
+    H, W = img.shape[:2]
+    q, r = _q32(mapx), _q32(mapy)
+    x0, fx, y0, fy = q >> 5, q & 31, r >> 5, r & 31
+    acc = np.zeros(q.shape + (3,), np.int64)
+    for dy, wy in ((0, 32 - fy), (1, fy)):
+        for dx, wx in ((0, 32 - fx), (1, fx)):
+            xx, yy = x0 + dx, y0 + dy
+            ok = (xx >= 0) & (xx < W) & (yy >= 0) & (yy < H)
+            val = np.zeros_like(acc)
+            val[ok] = img[yy[ok], xx[ok]]
+            acc += val * (wy * wx)[..., None]
+    return ((acc + 512) >> 10).astype(np.uint8)
+
+
+# ------------------------------------------------------------------------------------------------ _getProjectorMapping
+def projector_map(g, x0, y0, w, h):
+    """float32 (mapx, mapy) [h, w] of active.py:459-488 for the roi: projectPoints of the INTEGER pixel coordinates"""
+    yy, xx = np.mgrid[0:h, 0:w]
+    with np.errstate(all="ignore"):
+        Xa, Ya, _ = C.project_points(np.asarray(g, dtype=np.float64), (xx + x0).astype(np.float64), (yy + y0).astype(np.float64))
+        return Xa.astype(np.float32), Ya.astype(np.float32)
+
+
+def reference_image(fringe_gray, g, x0, y0, w, h):
+    mx, my = projector_map(g, x0, y0, w, h)
+    return remap_cubic(fringe_gray, mx, my)
+
+
+# ------------------------------------------------------------------------------------------------ findCentralStripe
+def stripe_centroids(img, color="r", sensitivity=0.5):
+    """active.py:305-333 as written: x [h], NaN where the row holds no stripe"""
+    fringe = img[:, :, CHANNEL[color]].copy()
+    fringe[fringe < 255 * sensitivity] = 0
+    i = np.arange(img.shape[1]).reshape(1, -1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.sum(fringe * i, axis=1) / np.sum(fringe, axis=1)
+
+
+def fill_linear(y, x):
+    """scipy's interp1d(y[valid], x[valid], kind="linear", fill_value="extrapolate")(y), its formula in numpy"""
+    valid = ~np.isnan(x)
+    ky, kx = y[valid], x[valid]
+    hi = np.searchsorted(ky, y).clip(1, ky.size - 1).astype(int)
+    lo = hi - 1
+    slope = (kx[hi] - kx[lo]) / (ky[hi] - ky[lo])
+    return slope * (y - ky[lo]) + kx[lo]
+
+
+def find_central_stripe(img, color="r", sensitivity=0.5):
+    x = stripe_centroids(img, color, sensitivity)
+    if np.isnan(x).all():
+        return None
+    y = np.arange(0.5, img.shape[0], 1)
+    return np.vstack((fill_linear(y, x), y)).T
+
+
+# ------------------------------------------------------------------------------------------------ the camera model
+def _dist(d):
+    v = np.zeros(12)
+    v[:len(d)] = d
+    return v
+
+
+def _distort(x, y, d):
+    k1, k2, p1, p2, k3, k4, k5, k6, s1, s2, s3, s4 = d
+    r2 = x * x + y * y
+    r4 = r2 * r2
+    r6 = r4 * r2
+    kr = (1 + k1 * r2 + k2 * r4 + k3 * r6) / (1 + k4 * r2 + k5 * r4 + k6 * r6)
+    xd = x * kr + 2 * p1 * x * y + p2 * (r2 + 2 * x * x) + s1 * r2 + s2 * r4
+    yd = y * kr + p1 * (r2 + 2 * y * y) + 2 * p2 * x * y + s3 * r2 + s4 * r4
+    return xd, yd
+
+
+def project(Pw, R, T, K, d):
+    """cv2.projectPoints(Pw [n, 3], R 3x3, T, K, d) -> [n, 2]"""
+    X = Pw.dot(R.T) + T.reshape(1, 3)
+    xd, yd = _distort(X[:, 0] / X[:, 2], X[:, 1] / X[:, 2], _dist(d))
+    return np.stack([K[0, 0] * xd + K[0, 2], K[1, 1] * yd + K[1, 2]], axis=1)
+
+
+def undistort_points(pts, K, d, Rm=None, iterations=5):
+    """cv2.undistortPoints(pts [n, 2], K, d, R = Rm): five fixed-point iterations, then the 3x3 Rm (P folded in)"""
+    k1, k2, p1, p2, k3, k4, k5, k6, s1, s2, s3, s4 = _dist(d)
+    x0 = (pts[:, 0] - K[0, 2]) / K[0, 0]
+    y0 = (pts[:, 1] - K[1, 2]) / K[1, 1]
+    x, y = x0.copy(), y0.copy()
+    for _ in range(iterations):
+        r2 = x * x + y * y
+        icdist = (1 + ((k6 * r2 + k5) * r2 + k4) * r2) / (1 + ((k3 * r2 + k2) * r2 + k1) * r2)
+        dx = 2 * p1 * x * y + p2 * (r2 + 2 * x * x) + s1 * r2 + s2 * r2 * r2
+        dy = p1 * (r2 + 2 * y * y) + 2 * p2 * x * y + s3 * r2 + s4 * r2 * r2
+        x = (x0 - dx) * icdist
+        y = (y0 - dy) * icdist
+    if Rm is not None:
+        X = Rm[0, 0] * x + Rm[0, 1] * y + Rm[0, 2]
+        Y = Rm[1, 0] * x + Rm[1, 1] * y + Rm[1, 2]
+        Wc = Rm[2, 0] * x + Rm[2, 1] * y + Rm[2, 2]
+        x, y = X / Wc, Y / Wc
+    return np.stack([x, y], axis=1)
+
+
+def perspective(pts, H):
+    q = np.hstack((pts, np.ones((pts.shape[0], 1)))).dot(H.T)
+    return q[:, :2] / q[:, 2:]
+
+
+def undistort_maps(K, d, size):
+    """cv2.initUndistortRectifyMap(K, d, I, K, size, CV_32FC1)"""
+    w, h = size
+    iR = np.linalg.inv(K.dot(np.eye(3)))
+    u, v = np.meshgrid(np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64))
+    X = iR[0, 0] * u + iR[0, 1] * v + iR[0, 2]
+    Y = iR[1, 0] * u + iR[1, 1] * v + iR[1, 2]
+    Wc = iR[2, 0] * u + iR[2, 1] * v + iR[2, 2]
+    xd, yd = _distort(X / Wc, Y / Wc, _dist(d))
+    return (K[0, 0] * xd + K[0, 2]).astype(np.float32), (K[1, 1] * yd + K[1, 2]).astype(np.float32)
+
+
+class Rig:
+    """What StereoFTP.__init__ derives from a rig dict of _ftp_cloud_ref.rig_params (active.py:385-401, _rigs.py, rectification.py:271-302)"""
+
+    def __init__(self, rig, period, fringe_width, shift=0):
+        self.K1, self.K2 = np.array(rig["intrinsic1"], dtype=np.float64), np.array(rig["intrinsic2"], dtype=np.float64)
+        self.R, self.T = np.array(rig["R"], dtype=np.float64).reshape(3, 3), np.array(rig["T"], dtype=np.float64).reshape(3, 1)
+        self.d1, self.d2, self.res1 = list(rig["distCoeffs1"]), list(rig["distCoeffs2"]), tuple(rig["res1"])
+        self.period, self.fp = period, 1 / period
+        self.peak = central_peak(fringe_width, period, shift)
+        v = self.K1.dot(self.R.T).dot(self.T).ravel()
+        vv = np.array([[0, -v[2], v[1]], [v[2], 0, -v[0]], [-v[1], v[0], 0]])
+        self.F = (np.linalg.inv(self.K2).T).dot(self.R).dot(self.K1.T).dot(vv)
+        Po2 = self.K2.dot(np.hstack((self.R, self.T)))
+        B = -np.linalg.inv(Po2[:, :3]).dot(Po2[:, 3])
+        v2 = np.cross([0, 0, 1], B)
+        v3 = np.cross(B, v2)
+        Rot = np.array([B / np.linalg.norm(B), v2 / np.linalg.norm(v2), v3 / np.linalg.norm(v3)])
+        self.Rectify1 = Rot.dot(np.linalg.inv(self.K1))
+        self.Rectify2 = Rot.dot(np.linalg.inv(self.R)).dot(np.linalg.inv(self.K2))
+        self.R_inv = np.linalg.inv(Rot)
+        self.baseline = np.linalg.norm(B)
+
+
+def triangulate(rg, cam_points, p_x, roi):
+    """active.py:561-605"""
+    cam = np.array(cam_points, dtype=np.float64).reshape(-1, 2)
+    n = cam.shape[0]
+    cam[:, 0] += roi[0]
+    cam[:, 1] += roi[1]
+    lines = np.hstack((cam, np.ones((n, 1)))).dot(rg.F.T)
+    p_x = np.full((n,), p_x, dtype=np.float64)
+    p_y = -(lines[:, 0] * p_x + lines[:, 2]) / lines[:, 1]
+    pc = perspective(cam, rg.Rectify1)
+    pp = undistort_points(np.stack([p_x, p_y], axis=1), rg.K2, rg.d2, rg.K2)
+    pp = perspective(pp, rg.Rectify2)
+    disparity = np.abs(pp[:, [0]] - pc[:, [0]])
+    pw = rg.baseline * (np.hstack((pc, np.ones((n, 1)))) / disparity)
+    return pw.dot(rg.R_inv.T)
+
+
+def camera_frequency(rg, obj_points):
+    """active.py:495-559; float32 where cv2 returns float32: pCenter and the undistorted points"""
+    Op = (-np.linalg.inv(rg.R).dot(rg.T)).flatten()
+    obj = np.asarray(obj_points).reshape(-1, 3).astype(np.float32)
+    n = obj.shape[0]
+    pCenter = project(obj.astype(np.float64), rg.R, rg.T, rg.K2, rg.d2).astype(np.float32)
+    half = np.float32((1 / rg.fp) / 2)
+    points = np.vstack((np.stack([pCenter[:, 0] - half, pCenter[:, 1]], axis=1),
+                        np.stack([pCenter[:, 0] + half, pCenter[:, 1]], axis=1)))
+    und = undistort_points(points.astype(np.float64), rg.K2, rg.d2, rg.K2).astype(np.float32)
+    pp = np.hstack((und, np.ones((2 * n, 1), dtype=np.float32)))
+    z = np.tile(obj[:, 2].reshape(-1, 1), (2, 1))
+    hh = np.linalg.inv(rg.K2.dot(rg.R)).dot(pp.T).T
+    s = (z - Op[2]) / hh[:, [2]]
+    pw = s * hh + Op.reshape(1, 3)
+    pc = project(pw, np.eye(3), np.zeros(3), rg.K1, rg.d1)
+    a, b = pc[:n], pc[n:]
+    Tc = ((a[:, 0] - b[:, 0]) ** 2 + (a[:, 1] - b[:, 1]) ** 2) / np.abs(a[:, 0] - b[:, 0])
+    return 1 / Tc
+
+
+# ------------------------------------------------------------------------------------------------ fringes
+def central_peak(length, period, shift=0):
+    k = (length / 2) // period
+    return period * (k - shift / (2 * np.pi))
+
+
+def build_fringe(period, shift=0, dims=(1280, 720), stripeColor=None):
+    """active.py:87-148 for a horizontal uint8 fringe"""
+    row = ((1 + np.cos(2 * np.pi * (1 / period) * (np.arange(dims[0], dtype=float) + shift))) / 2)[np.newaxis, :]
+    row *= 255
+    if stripeColor is not None:
+        row = np.repeat(row[:, :, np.newaxis], 3, axis=2)
+        peak = central_peak(dims[0], period, shift)
+        left = int(peak - period / 2)
+        right = int(left + period)
+        for ch in range(3):
+            if ch != CHANNEL[stripeColor]:
+                row[0, left:right, ch] = 0
+    return np.repeat(row.astype(np.uint8), dims[1], axis=0)
+
+
+def render(rig, period, fringe_dims=(1280, 720), z0=1000.0, bump=8.0, amplitude=1.0):
+    """The uint8 BGR frame a camera of `rig` sees of the surface Z = z0 + bump * exp(-((X / 30)^2 + (Y / 20)^2)) lit by
+    build_fringe(period, stripeColor='r') of `fringe_dims`: per camera pixel the ray (lens distortion undone), its point on
+    the surface, that point on the projector, and the fringe evaluated analytically there (0 outside the projector image)."""
+    rg = Rig(rig, period, fringe_dims[0])
+    w, h = rg.res1
+    v, u = np.mgrid[0:h, 0:w].astype(np.float64)
+    n = undistort_points(np.stack([u.ravel(), v.ravel()], axis=1), rg.K1, rg.d1)
+    Z = np.full(n.shape[0], z0)
+    for _ in range(20):
+        Z = z0 + bump * np.exp(-((n[:, 0] * Z / 30.0) ** 2 + (n[:, 1] * Z / 20.0) ** 2))
+    Pw = np.stack([n[:, 0] * Z, n[:, 1] * Z, Z], axis=1)
+    pp = project(Pw, rg.R, rg.T, rg.K2, rg.d2)
+    inside = (pp[:, 0] >= 0) & (pp[:, 0] <= fringe_dims[0] - 1) & (pp[:, 1] >= 0) & (pp[:, 1] <= fringe_dims[1] - 1)
+    val = np.where(inside, amplitude * 255 * (1 + np.cos(2 * np.pi * pp[:, 0] / period)) / 2, 0.0)
+    left = int(rg.peak - period / 2)
+    stripe = (pp[:, 0] >= left) & (pp[:, 0] < int(left + period))
+    img = np.repeat(np.rint(val)[:, None], 3, axis=1)
+    img[stripe, :2] = 0
+    return img.reshape(h, w, 3).astype(np.uint8)
+
+
+# ------------------------------------------------------------------------------------------------ the pipeline
+def pipeline(rig, fringe, period, frame, roi=None, radius_factor=0.5, phase_of=None):
+    """StereoFTP(rig, fringe, period).getCloud(frame, radius_factor, roi) in numpy (active.py:631-841) -> dict of every stage.
+    `phase_of(obj, ref, fc, radius_factor)` replaces the np.fft demodulation (e.g. the np.longdouble phase of _ftp_ref)."""
+    rg = Rig(rig, period, fringe.shape[1])
+    gray = np.max(fringe, axis=2)
+    W, H = rg.res1
+    mx, my = undistort_maps(rg.K1, rg.d1, rg.res1)
+    und = remap_linear(frame, mx, my)
+    x0, y0, w, h = (0, 0, W, H) if roi is None else roi
+    cut = np.ascontiguousarray(und[y0:y0 + h, x0:x0 + w])
+    stripe = find_central_stripe(cut, "r", 0.5)
+    idx = np.ceil(stripe - 0.5).astype(np.int64)
+    world = triangulate(rg, stripe, rg.peak, (x0, y0, w, h))
+    z_plane = np.mean(world[:, 2])
+    fc = camera_frequency(rg, world)
+    g, fp = C.geometry(rig, z_plane, period)
+    ref = reference_image(gray, g, x0, y0, w, h)
+    fmin, fmax = P.band(fc, radius_factor, h)
+    wrapped = (phase_of or P.ftp_phase_numpy)(cut, ref, fc, radius_factor)
+    phase = np.unwrap(np.unwrap(wrapped, discont=np.pi, axis=1), discont=np.pi, axis=0)
+    k = C.fringe_order(g, fp, phase, idx, rg.peak, x0, y0)
+    cloud = C.cloud_from_geometry(g, phase, k, x0, y0)
+    return {"undistorted": cut, "stripe": stripe, "stripe_indexes": idx, "z_plane": z_plane, "fc": fc, "geom": g, "ref": ref,
+            "fmin": fmin, "fmax": fmax, "wrapped": wrapped, "phase": phase, "k": k, "cloud": cloud}
+
+
+# ------------------------------------------------------------------------------------------------ golden cases
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+_CASES = {}
+
+
+def load_cases(kind):
+    """The "reference" or "cloud" cases of tests/golden/stereo_ftp_cases.{json,npz} (make_golden_stereo_ftp.py):
+    {name: json entry + its arrays}; loaded once and shared, read-only"""
+    if not _CASES:
+        with open(os.path.join(GOLDEN, "stereo_ftp_cases.json")) as f:
+            meta = json.load(f)
+        z = np.load(os.path.join(GOLDEN, "stereo_ftp_cases.npz"))
+        for k in ("reference", "cloud"):
+            _CASES[k] = {}
+            for name, c in meta[k].items():
+                c = dict(c, period=meta["period"])
+                for key in z.files:
+                    if key.startswith(name + "__"):
+                        c[key[len(name) + 2:]] = z[key]
+                        c[key[len(name) + 2:]].setflags(write=False)
+                _CASES[k][name] = c
+    return _CASES[kind]
+
+
+def case_fringe(c):
+    """The gray fringe of a "reference" case: the gray of build_fringe(period, stripeColor='r'), or seeded random bytes"""
+    if c["fringe"] == "cos":
+        return np.max(build_fringe(c["period"], stripeColor="r"), axis=2)
+    wp, hp = c["fringe"]
+    return np.random.default_rng(wp * 1000 + hp).integers(0, 256, (hp, wp), dtype=np.uint8)
