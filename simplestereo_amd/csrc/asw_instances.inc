@@ -12,10 +12,8 @@ SSAMD_PIPE_INSTANCE(true, 88, 348, 272)
 SSAMD_PIPE_INSTANCE(true, 216, 284, 80)
 #endif
 #ifdef SSAMD_WAVE6_INSTANCE
-SSAMD_WAVE6_INSTANCE(true, 0, false)
-SSAMD_WAVE6_INSTANCE(false, 0, false)
-SSAMD_WAVE6_INSTANCE(false, 2, false)
-SSAMD_WAVE6_INSTANCE(false, 2, true)
-SSAMD_WAVE6_INSTANCE(false, 3, false)
-SSAMD_WAVE6_INSTANCE(false, 3, true)
+SSAMD_WAVE6_INSTANCE(true, 0)
+SSAMD_WAVE6_INSTANCE(false, 0)
+SSAMD_WAVE6_INSTANCE(false, 2)
+SSAMD_WAVE6_INSTANCE(false, 3)
 #endif

@@ -107,9 +107,10 @@ bool asw_layout_e(AswGeom &g, const PlanOptions &po, int win, int XG, int DG, si
         g.off_bgrR = take((size_t)g.nR * 4 * 2);
     }
     g.lds_bytes = (int)off;
-    // the phase-shifted kernel normally runs with the TAD volume and then does not allocate the staged colour bytes: a tile may
-    // count on that (round 4); a call that cannot have the volume re-plans with PlanOptions::no_volume set (asw_replan_without_volume)
-    if (g.pipe && po.t.asw_evol != 0 && po.t.lds_relax != 0 && !po.no_volume) return (size_t)g.lds_bytes_evol <= limit;
+    // the phase-shifted kernel normally runs with the TAD volume and then does not allocate the staged colour bytes: a tile is
+    // planned on that (round 4, profiles/r04_lds_relax_ab.txt) unless SSAMD_ASW_EVOL=0 says there will be no volume; a call that
+    // cannot have the volume after all re-plans with PlanOptions::no_volume set (asw_final_volume)
+    if (g.pipe && po.t.asw_evol != 0 && !po.no_volume) return (size_t)g.lds_bytes_evol <= limit;
     return off <= limit;
 }
 
@@ -219,7 +220,7 @@ bool asw_wave_layout_one(AswWaveGeom &g, const PlanOptions &po, int win, int DG,
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 15) & ~(size_t)15; return (int)o; };
     g.off_w = take((size_t)(g.SLw + g.SRw) * 4 * 2);        // two rows: tap columns j and j + 1
-    // centres in registers (asw_aggregate_wave_kernel<..., CREG>): four-per-lane, 4-column tile, merged build of at most four rounds
+    // centres in registers (CREG, asw_wave_front.inc): 4-column tile, merged build of two to four rounds (to three: six per lane)
     g.creg = creg && merged && rx == 4 && g.K >= 2 && (rd == 6 ? g.K <= 3 : g.K <= 4) ? 1 : 0;      // (the instantiations that exist)
     g.off_cen = take(g.creg ? 0 : (size_t)(g.Txw + g.nRcw) * 16);
     g.off_pixL = take((size_t)g.nLw * 16);
@@ -245,7 +246,6 @@ bool asw_wave_layout(AswWaveGeom &g, const PlanOptions &po, int win, int nD, int
 {
     const bool never6 = (rx & 16) != 0;
     rx &= 15;
-    creg = creg && po.t.wave_creg != 0;
     const int DG = (nD + ASW_RD - 1) / ASW_RD;
     if (DG < 1 || DG > ASW_WAVE_MAX_DG) return false;
     const int nxg_max = 64 / DG;
@@ -259,7 +259,6 @@ bool asw_wave_layout(AswWaveGeom &g, const PlanOptions &po, int win, int nD, int
     for (int nxg = nxg_max; nxg >= std::max(1, nxg_max - 4); --nxg)
         for (int merged = 0; merged <= 1; ++merged) {
             AswWaveGeom c;
-            if (merged && nxg != nxg_max && po.t.wave_merge == 2) continue;
             if (!asw_wave_layout_one(c, po, win, DG, rx, nxg, merged != 0, ASW_RD, creg)) continue;
             if (merged && c.K > 4) continue;
             if (!merged && nxg != nxg_max) continue;     // fewer column groups only pay through a saved merged round

@@ -37,18 +37,19 @@ __device__ __forceinline__ void asw_row_unpack6(AswRow6 &row, const uint2 packed
 }
 
 // KM: build rounds known at compile time (3 for the class default), 0: counted at run time
-// CREG: window centres in registers (asw_wave_front.inc): no cen array in LDS, two instead of three reads per weight pair.
+// A straight-line build keeps the window centres in registers (CREG, asw_wave_front.inc): no cen array in LDS, two instead of
+// three reads per weight pair.
 // (Round 4 also built a 128-VGPR form -- four waves per SIMD, build rounds one after the other -- and an e tile without its spare
 //  slot, Se = 24: the 96 registers of accumulators and e window leave too little, 6.49 vs 6.07 ms at 1080p / D 0..16 and 4.15 vs
 //  3.45 ms with register centres; Se = 24 bought a resident wave at win >= 31 and cost 10-16 % below.  profiles/r04_wave6_*.txt.)
-template <bool WITH_COSTS, int KM, bool CREG = false>
+template <bool WITH_COSTS, int KM>
 __global__ __launch_bounds__(256, 3) void asw_aggregate_wave6_kernel(const AswWaveArgs A)
 {
-    static_assert(!CREG || KM > 0, "register centres need the straight-line build");
-    // build_merged keeps all reads of a straight-line build in flight for RX == 4 && KM <= 3 and goes round by round above that;
-    // every instance (asw_instances.inc: KM 0, 2, 3) is built the first way, and a fourth round has to be measured before it ships
-    static_assert(KM <= 3, "asw_wave_front.inc: KM > 3 selects the serial build, which this kernel has never been measured with");
+    // the register-centre build keeps 2 KM tap reads in flight next to 96 registers of accumulators and e window; every instance
+    // (asw_instances.inc: KM 0, 2, 3) is measured, and a fourth round has to be measured before it ships
+    static_assert(KM <= 3, "asw_wave_front.inc: a register-centre build of KM > 3 rounds has never been measured with this kernel");
     constexpr int RX = 4, RD = 6, NWR = 10;          // nine right weights used, read as five pairs
+    constexpr bool CREG = KM > 0;                    // (AswWaveGeom::creg must agree: asw_pick_wave_kernel)
     // ---- LDS slice, strip, accumulators, window centres, the merged support-weight build: shared with asw_aggregate_wave_kernel
 #include "asw_wave_front.inc"
     auto build = [&](int j, float pj0, float pj1) { build_merged(sbase + g.off_pixL + 16 * j, sbase + g.off_cen, sbase + g.off_w, pj0, pj1); };

@@ -7,7 +7,7 @@
 #include "asw_wave6_kernel.hip.h"
 
 namespace ssamd {
-#define SSAMD_WAVE6_INSTANCE(C, K, CREG) template __global__ void asw_aggregate_wave6_kernel<C, K, CREG>(const AswWaveArgs);
+#define SSAMD_WAVE6_INSTANCE(C, K) template __global__ void asw_aggregate_wave6_kernel<C, K>(const AswWaveArgs);
 #include "asw_instances.inc"
 #undef SSAMD_WAVE6_INSTANCE
 }  // namespace ssamd

@@ -2,10 +2,12 @@
 // the early exits, the cleared accumulators, the window centres (in registers or in LDS), the LDS address helpers and the merged
 // support-weight build of two tap columns.  Included ONCE, as the first statements of the kernel body after the kernel's own
 // constants; asw_wave_row.inc (inside the loop over window rows) and asw_epilogue.inc (last) use the names it defines.
-// Text, not functions: with the staging block and the best-row clear as lambdas the same statements changed all 24 instances of
-// the two kernels (DESIGN 4.7); tools/isa_compare.py holds an edit here to its intent.
+// Text, not functions: with the staging block and the best-row clear as lambdas the same statements changed every instance of
+// the two kernels (24 then, DESIGN 4.7); tools/isa_compare.py holds an edit here to its intent.
 //
-// Read by name:      A (AswWaveArgs), threadIdx, blockIdx; template parameters KM, CREG; RX and RD (columns and disparities per
+// Read by name:      A (AswWaveArgs), threadIdx, blockIdx; template parameter KM; the constant CREG each kernel derives from its
+//                    template parameters (4-column tile and KM > 0: the straight-line merged build has its centres in registers;
+//                    without them a straight-line merged build is the 8-column tile's); RX and RD (columns and disparities per
 //                    lane: the second extent of accN / accS), which the wave kernel has as template parameter / constant and the
 //                    six-per-lane kernel as constants.
 // Defined, used by the kernels, asw_wave_row.inc and asw_epilogue.inc:
@@ -101,7 +103,7 @@
     // last rounds (class default D 0..16, 4-column tile: 48 + 67 centres = 2 rounds instead of 1 + 2); 0: counted at run time.
     // The two parts read different pixel rows; pixR follows pixL in LDS, so the tap address of list entry c is
     // pixL + 16 (c + j) + (c < Txw ? 0 : 32 pad): one per-lane constant per round (tapoff), set up once per wave.
-    // CREG (round 4, with KM > 0): the centres a lane evaluates are the SAME in every build of the kernel (list entries lane,
+    // CREG (round 4; 4-column tile, KM > 0): the centres a lane evaluates are the SAME in every build of the kernel (list entries lane,
     // lane + 64, ...), so their Lab values are loaded once from the records into 3 KM registers (cenx/y/z above) instead of being
     // kept in an LDS array and re-read twice per tap-column pair: a third fewer LDS reads per weight, and the wave's LDS slice
     // loses 16 bytes per centre -- at D 0..7 / win 35 (124-column strips, 255 centres) that is 13.9 -> 9.9 KB, 11 -> 16 resident
@@ -133,24 +135,8 @@
             }
             return;
         }
-        if constexpr (KM > 0) {
+        if constexpr (KM > 0) {                          // centres in LDS, round by round: the 8-column tile (no registers for more)
             const uint32_t ca = cen_b + lane16, da = dst_b + lane4, db_ = da + row1;
-            if constexpr (RX == 4 && KM <= 3) {          // registers to spare: all reads of the build in flight together
-                float4 ce[KM], ta_[KM], tb[KM];
-#pragma unroll
-                for (int r = 0; r < KM; ++r) {
-                    const uint32_t ta = tap_b + tapoff[r];
-                    ce[r] = ld4(ca + 1024 * r); ta_[r] = ld4(ta); tb[r] = ld4(ta + 16);
-                }
-#pragma unroll
-                for (int r = 0; r < KM; ++r) asm volatile("" ::"v"(ce[r].w), "v"(ta_[r].w), "v"(tb[r].w) : "memory");
-#pragma unroll
-                for (int r = 0; r < KM; ++r) {
-                    *(lds_f1)(da + 256 * r) = weight(ce[r], ta_[r], pj0);
-                    *(lds_f1)(db_ + 256 * r) = weight(ce[r], tb[r], pj1);
-                }
-                return;
-            }
 #pragma unroll
             for (int r = 0; r < KM; ++r) {
                 const uint32_t ta = tap_b + tapoff[r];

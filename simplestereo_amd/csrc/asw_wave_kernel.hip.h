@@ -70,13 +70,14 @@ __device__ __forceinline__ void asw_wave_order()
 
 // KL, KR: build rounds (64 centres each) of the left and of the right part when the host knows them at compile time
 // (the build is then straight-line code with immediate offsets); 0: counted at run time.
-// KM (round 3): rounds of the MERGED build, CREG (round 4, with KM > 0): the window centres in registers -- both are
-// explained with the build they select, in asw_wave_front.inc.
-template <bool WITH_COSTS, int RX, int KL = 0, int KR = 0, int KM = 0, bool CREG = false>
+// KM (round 3): rounds of the MERGED build; CREG (round 4): the window centres in registers, which is what the straight-line
+// merged build of the 4-column tile does -- both are explained with the build they select, in asw_wave_front.inc.
+template <bool WITH_COSTS, int RX, int KL = 0, int KR = 0, int KM = 0>
 __global__ __launch_bounds__(256, RX == 8 ? 3 : 4) void asw_aggregate_wave_kernel(const AswWaveArgs A)
 {
-    static_assert(!CREG || KM > 0, "register centres need the straight-line merged build");
+    static_assert((KL == 0 && KR == 0) || RX == 8, "straight-line separate rounds: measured and instantiated with the 8-column tile only");
     constexpr int NWR = asw_nwr(RX), RD = ASW_RD;
+    constexpr bool CREG = RX == 4 && KM > 0;         // (AswWaveGeom::creg must agree: asw_pick_wave_kernel)
     // ---- LDS slice, strip, accumulators, window centres, the merged support-weight build: shared with asw_aggregate_wave6_kernel
 #include "asw_wave_front.inc"
     // the separate-rounds build (KL / KR, or counted): the left and the right part of the centre list one after the other
@@ -84,21 +85,8 @@ __global__ __launch_bounds__(256, RX == 8 ? 3 : 4) void asw_aggregate_wave_kerne
         asm volatile("" : "+s"(tap_b), "+s"(cen_b), "+s"(dst_b));        // opaque: base + lane sums are formed here, per build
         const uint32_t row1 = (uint32_t)wrow * 4;
         constexpr int K = decltype(rounds)::value;
-        if constexpr (K > 0) {                           // round count known: one address per array, immediate offsets
+        if constexpr (K > 0) {                           // round count known (8-column tile only): one address per array, immediate offsets
             const uint32_t ca = cen_b + lane16, ta = tap_b + lane16, da = dst_b + lane4, db_ = da + row1;
-            if constexpr (RX == 4 && K <= 3) {           // registers to spare: all reads of the part in flight together
-                float4 ce[K], ta_[K], tb[K];
-#pragma unroll
-                for (int r = 0; r < K; ++r) { ce[r] = ld4(ca + 1024 * r); ta_[r] = ld4(ta + 1024 * r); tb[r] = ld4(ta + 1024 * r + 16); }
-#pragma unroll
-                for (int r = 0; r < K; ++r) asm volatile("" ::"v"(ce[r].w), "v"(ta_[r].w), "v"(tb[r].w) : "memory");
-#pragma unroll
-                for (int r = 0; r < K; ++r) {
-                    *(lds_f1)(da + 256 * r) = weight(ce[r], ta_[r], pj0);
-                    *(lds_f1)(db_ + 256 * r) = weight(ce[r], tb[r], pj1);
-                }
-                return;
-            }
 #pragma unroll
             for (int r = 0; r < K; ++r) {
                 const float4 ce0 = ld4(ca + 1024 * r), ta0 = ld4(ta + 1024 * r), tb0 = ld4(ta + 1024 * r + 16);

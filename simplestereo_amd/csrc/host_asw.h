@@ -65,21 +65,25 @@ const AswPipeVariant kPipeVariants[] = {
 };
 // Wave kernels: RD disparities per lane (6: asw_instances.inc; 4: instantiated here), RX columns, and the build rounds known at
 // compile time (straight-line build) for the common combinations; KM > 0: merged build of KM rounds, else KL + KR separate rounds
-struct AswWaveVariant { int RD; bool costs; int RX, KL, KR, KM; bool creg; AswWaveKernel kernel; };
-#define SSAMD_WAVE_VARIANT(RX, KL, KR, KM, CREG) {4, false, RX, KL, KR, KM, CREG, asw_aggregate_wave_kernel<false, RX, KL, KR, KM, CREG>}
+// (a straight-line merged build of the 4-column tile keeps the window centres in registers, AswWaveGeom::creg: the kernels derive that)
+// Row comments: the disparity counts nD at which the default plan of a plain call selects the row, and those at which only one
+// of the autotuner's other candidates does (the other tile, never six per lane); enumerated from asw_plan.h over nD 1..64,
+// profiles/wave_variants_retired.txt.  The six-per-lane rows (asw_instances.inc): KM 3 default 17..18, tuner 21..24; KM 2 tuner
+// only, 29..30 and 33..60.  Every other strip -- SSAMD_ASW_WAVE_MERGE=0 with the 4-column tile among them -- runs the generic kernel.
+struct AswWaveVariant { int RD; bool costs; int RX, KL, KR, KM; AswWaveKernel kernel; };
+#define SSAMD_WAVE_VARIANT(RX, KL, KR, KM) {4, false, RX, KL, KR, KM, asw_aggregate_wave_kernel<false, RX, KL, KR, KM>}
 const AswWaveVariant kWaveVariants[] = {
-#define SSAMD_WAVE6_INSTANCE(C, K, CREG) {6, C, 4, 0, 0, K, CREG, asw_aggregate_wave6_kernel<C, K, CREG>},
+#define SSAMD_WAVE6_INSTANCE(C, K) {6, C, 4, 0, 0, K, asw_aggregate_wave6_kernel<C, K>},
 #include "asw_instances.inc"
 #undef SSAMD_WAVE6_INSTANCE
-    SSAMD_WAVE_VARIANT(4, 0, 0, 2, false), SSAMD_WAVE_VARIANT(4, 0, 0, 2, true),      // class default D 0..16 four per lane: 48 + 67 centres
-    SSAMD_WAVE_VARIANT(4, 0, 0, 3, false), SSAMD_WAVE_VARIANT(4, 0, 0, 3, true),
-    SSAMD_WAVE_VARIANT(4, 0, 0, 4, false), SSAMD_WAVE_VARIANT(4, 0, 0, 4, true),
-    SSAMD_WAVE_VARIANT(8, 0, 0, 2, false), SSAMD_WAVE_VARIANT(8, 0, 0, 3, false), SSAMD_WAVE_VARIANT(8, 0, 0, 4, false),
-    SSAMD_WAVE_VARIANT(8, 2, 2, 0, false),      // 17..28 disparities (class default)
-    SSAMD_WAVE_VARIANT(8, 1, 2, 0, false),      // 29..48
-    SSAMD_WAVE_VARIANT(4, 1, 2, 0, false),      // 13..20
-    SSAMD_WAVE_VARIANT(4, 2, 2, 0, false),      // 9..12
-    SSAMD_WAVE_VARIANT(4, 2, 3, 0, false),      // 5..8
+    SSAMD_WAVE_VARIANT(4, 0, 0, 2),      // default 13..16, 19..20 (class default D 0..16 four per lane: 48 + 67 centres); tuner 17..18, 61..64
+    SSAMD_WAVE_VARIANT(4, 0, 0, 3),      // default 9..12
+    SSAMD_WAVE_VARIANT(4, 0, 0, 4),      // default 5..8
+    SSAMD_WAVE_VARIANT(8, 0, 0, 2),      // default 41..64
+    SSAMD_WAVE_VARIANT(8, 0, 0, 3),      // default 21..28
+    SSAMD_WAVE_VARIANT(8, 0, 0, 4),      // tuner only, 13..16
+    SSAMD_WAVE_VARIANT(8, 2, 2, 0),      // tuner only, 17..20 (SSAMD_ASW_WAVE_MERGE=0: 17..28)
+    SSAMD_WAVE_VARIANT(8, 1, 2, 0),      // default 29..40 (SSAMD_ASW_WAVE_MERGE=0: 29..64)
 };
 #undef SSAMD_WAVE_VARIANT
 
@@ -97,13 +101,15 @@ AswKernel asw_pick_pipe_kernel(const AswGeom &g, bool costs, int asw_static)
     return pk;
 }
 
-// A miss runs the generic instantiation of the family (no straight-line build, centres in LDS).
+// A miss runs the generic instantiation of the family (no straight-line build, centres in LDS) -- also a variant whose centres are
+// not where the strip's LDS layout (g.creg) has them.
 AswWaveKernel asw_pick_wave_kernel(const AswWaveGeom &g, bool costs, bool unrolled)
 {
     const bool straight = unrolled && !costs;
     const int kl = g.merged ? 0 : (g.Txw + 63) / 64, kr = g.merged ? 0 : (g.nRcw + 63) / 64, km = g.merged ? g.K : 0;
     for (const AswWaveVariant &v : kWaveVariants)
-        if (straight && v.RD == g.RD && !v.costs && v.RX == g.RX && v.KL == kl && v.KR == kr && v.KM == km && v.creg == (g.creg != 0)) return v.kernel;
+        if (straight && v.RD == g.RD && !v.costs && v.RX == g.RX && v.KL == kl && v.KR == kr && v.KM == km &&
+            (v.RX == 4 && v.KM > 0) == (g.creg != 0)) return v.kernel;
     if (g.RD == 6) return costs ? asw_aggregate_wave6_kernel<true, 0> : asw_aggregate_wave6_kernel<false, 0>;
     return g.RX == 8 ? (costs ? asw_aggregate_wave_kernel<true, 8> : asw_aggregate_wave_kernel<false, 8>)
                      : (costs ? asw_aggregate_wave_kernel<true, 4> : asw_aggregate_wave_kernel<false, 4>);

@@ -33,7 +33,7 @@
 // the phase-shifted and the six-per-lane kernels are instantiated in translation units of their own (asw_pipe_tu.hip, asw_wave6_tu.hip)
 namespace ssamd {
 #define SSAMD_PIPE_INSTANCE(C, SL, SR, SE) extern template __global__ void asw_aggregate_pipe_kernel<C, SL, SR, SE>(const AswArgs);
-#define SSAMD_WAVE6_INSTANCE(C, K, CREG) extern template __global__ void asw_aggregate_wave6_kernel<C, K, CREG>(const AswWaveArgs);
+#define SSAMD_WAVE6_INSTANCE(C, K) extern template __global__ void asw_aggregate_wave6_kernel<C, K>(const AswWaveArgs);
 #include "asw_instances.inc"
 #undef SSAMD_PIPE_INSTANCE
 #undef SSAMD_WAVE6_INSTANCE

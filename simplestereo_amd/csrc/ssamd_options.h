@@ -16,7 +16,7 @@
     X("SSAMD_ASW_WAVE_RX", wave_rx, int, 0, atoi(v), x != 0)   /* 0 unset, 8 / 4: forced register tile of the wave kernel */ \
     X("SSAMD_ASW_WAVE_WG", wave_wg, int, 0, std::max(1, std::min(4, atoi(v))), x != 0)   /* 0 unset (one wave per workgroup), 1..4 */ \
     X("SSAMD_ASW_WAVE_UNROLL", wave_unroll, int, 1, atoi(v), false)   /* 0: counted build loop */ \
-    X("SSAMD_ASW_WAVE_MERGE", wave_merge, int, 1, atoi(v), x != 1)   /* 0: left and right centres of a strip in separate build rounds (round-2 form) */ \
+    X("SSAMD_ASW_WAVE_MERGE", wave_merge, int, 1, atoi(v), x == 0)   /* 0: separate rounds (left and right centres of a strip built one after the other, the round-2 form), else default */ \
     X("SSAMD_ASW_STATIC", asw_static, int, 1, atoi(v), x != 1)   /* 0: the phase-shifted kernel always reads its strides from the geometry (round-2 form); anything else: stride constants where an instantiation has the tile's */ \
     X("SSAMD_ASW_EVOL_MAX_MB", evol_max_mb, int, 0, std::max(0, atoi(v)), x != 0)   /* 0 unset; else a cap of the TAD volume in MiB (tests of the paths taken when memory is short) */ \
     X("SSAMD_ASW_WAVE_RD", wave_rd, int, 0, atoi(v), x != 0)   /* 0: the host decides; 4: never the six-disparities-per-lane form of the wave kernel */ \
@@ -28,8 +28,6 @@
     X("SSAMD_ASW_EVOL_FAIL", evol_fail, int, 0, atoi(v), false)   /* test hook: 1 = the TAD volume's allocation really fails (a hipMalloc no device can serve) */ \
     X("SSAMD_ASW_TAIL", asw_tail, int, -1, atoi(v), false)   /* -1: the host decides; 0: never split the last partial round of workgroups into half-width tiles; 1: whenever possible */ \
     X("SSAMD_ASW_PERSIST", asw_persist, int, -1, atoi(v), x > 0)   /* -1: the host decides; 0: the phase-shifted kernel always runs one workgroup per tile; n > 0: persistent form with min(n, resident slots) workgroups */ \
-    X("SSAMD_ASW_WAVE_CREG", wave_creg, int, 1, atoi(v), x != 1)   /* 0: the wave kernel keeps its window centres in LDS (round-3 form) */ \
-    X("SSAMD_ASW_LDS_RELAX", lds_relax, int, 1, atoi(v), x != 1)   /* 0: a phase-shifted tile must fit LDS with its staged colour bytes even when the TAD volume makes them unnecessary */ \
     X("SSAMD_ASW_PREPASS_FUSE", prepass_fuse, int, 1, atoi(v), false)   /* 0: Lab records and TAD volume as two dependent launches (the form of rounds 2-4) */ \
     X("SSAMD_EXACT_TOL", exact_tol, int, 128, std::max(0, atoi(v)), false)   /* fp64 tie-break pass: candidates within this many ulps of the winning cost image are re-evaluated */ \
     X("SSAMD_EXACT_CAP", exact_cap, int, 0, std::max(1, atoi(v)), false)   /* 0 unset: queue capacity of the tie-break pass in entries (test hook: a tiny queue overflows) */ \

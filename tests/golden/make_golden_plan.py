@@ -42,14 +42,11 @@ SWEEP = {
         {"SSAMD_ASW_EVOL": "0"},
         {"SSAMD_ASW_WAVE": "0", "SSAMD_ASW_PIPE": "0", "SSAMD_ASW_NO_E2": "1"},
         {"SSAMD_ASW_WAVE": "0", "SSAMD_ASW_PIPE": "0", "SSAMD_ASW_XOR_ONLY": "1"},
-        {"SSAMD_ASW_LDS_RELAX": "0"},
         {"SSAMD_ASW_WAVE_RX": "4"},
         {"SSAMD_ASW_WAVE_RX": "8"},
         {"SSAMD_ASW_WAVE_MERGE": "0"},
-        {"SSAMD_ASW_WAVE_MERGE": "2"},
         {"SSAMD_ASW_WAVE_RD": "4"},
         {"SSAMD_ASW_WAVE_WG": "4"},
-        {"SSAMD_ASW_WAVE_CREG": "0"},
         {"SSAMD_ASW_DEPHASE": "0"},
         {"SSAMD_ASW_GEOM": "3,5,8", "SSAMD_ASW_WAVE": "0"},
         {"SSAMD_ASW_GEOM": "6,4,16,8", "SSAMD_ASW_WAVE": "0"},

@@ -137,11 +137,10 @@ def test_half_width_tail_tiles(ss):
     assert n32 > 0
 
 
-# ---- wave kernel (asw_aggregate_wave_kernel): register tiles, merged build rounds, waves per workgroup, unrolling, creg
+# ---- wave kernel (asw_aggregate_wave_kernel): register tiles, merged build rounds, waves per workgroup, unrolling
 WAVE = [("8", {}, 128, None), ("4", {}, 128, None), ("8", dict(SSAMD_ASW_WAVE_MERGE="0"), 128, None),
         ("4", dict(SSAMD_ASW_WAVE_MERGE="0"), 128, None), ("8", dict(SSAMD_ASW_WAVE_WG="2"), 1000, 128),
-        ("4", dict(SSAMD_ASW_WAVE_WG="4"), 1000, 256), ("8", dict(SSAMD_ASW_WAVE_UNROLL="0"), 128, None),
-        ("4", dict(SSAMD_ASW_WAVE_CREG="0"), 128, None)]
+        ("4", dict(SSAMD_ASW_WAVE_WG="4"), 1000, 256), ("8", dict(SSAMD_ASW_WAVE_UNROLL="0"), 128, None)]
 
 
 @pytest.mark.parametrize("rx,extra,W,threads", WAVE)

@@ -1,5 +1,5 @@
 """The launch planner's decisions are pinned: tests/golden/plan_cases.npz holds what ssamd_asw_geometry, ssamd_asw_kernel_form
-and ssamd_gsw_geometry answered, for a sweep of shapes under 21 ASW and 11 GSW option sets, BEFORE the planner moved out of
+and ssamd_gsw_geometry answered, for a sweep of shapes under 18 ASW and 11 GSW option sets, BEFORE the planner moved out of
 the library's host code, then all in ssamd_api.hip (tests/golden/make_golden_plan.py).  Host arithmetic only: no GPU."""
 import importlib.util
 import json
@@ -43,14 +43,14 @@ def test_every_planner_decision_equals_the_recorded_one(plan):
 
 
 # Every option that forces a kernel form and is read by the planner, alone, with a value that changes a plan.  What the per-shape
-# cache holds is the workgroup geometry and which wave kernel serves the range.  Nine options change that, and dropping the forcing
-# condition of any of them fails the test (each tried): GEOM, PIPE, DEPHASE, EVOL, WAVE, WAVE_RX, NO_E2, XOR_ONLY, LDS_RELAX.  The
-# other six cannot be caught by a geometry query: WAVE_WG, WAVE_MERGE, WAVE_RD and WAVE_CREG only shape the wave kernel's strip, which
+# cache holds is the workgroup geometry and which wave kernel serves the range.  Eight options change that, and dropping the forcing
+# condition of any of them fails the test (each tried): GEOM, PIPE, DEPHASE, EVOL, WAVE, WAVE_RX, NO_E2, XOR_ONLY.  The
+# other five cannot be caught by a geometry query: WAVE_WG, WAVE_MERGE and WAVE_RD only shape the wave kernel's strip, which
 # is laid out anew for every query and never cached (no shape was found where they change the cached part), and the planner never
-# reads SSAMD_ASW_STATIC and SSAMD_ASW_EVOL_MAX_MB.  The four strip options are asked all the same.
+# reads SSAMD_ASW_STATIC and SSAMD_ASW_EVOL_MAX_MB.  The three strip options are asked all the same.
 FORCING = [("SSAMD_ASW_GEOM", "3,5,8"), ("SSAMD_ASW_PIPE", "0"), ("SSAMD_ASW_DEPHASE", "0"), ("SSAMD_ASW_EVOL", "0"), ("SSAMD_ASW_WAVE", "0"),
            ("SSAMD_ASW_WAVE_RX", "8"), ("SSAMD_ASW_WAVE_WG", "4"), ("SSAMD_ASW_WAVE_MERGE", "0"), ("SSAMD_ASW_WAVE_RD", "4"),
-           ("SSAMD_ASW_NO_E2", "1"), ("SSAMD_ASW_XOR_ONLY", "1"), ("SSAMD_ASW_WAVE_CREG", "0"), ("SSAMD_ASW_LDS_RELAX", "0")]
+           ("SSAMD_ASW_NO_E2", "1"), ("SSAMD_ASW_XOR_ONLY", "1")]
 
 _ORDERING_CHILD = r"""
 import json, sys
