@@ -1,4 +1,4 @@
-"""ctypes binding of libssamd.so (C ABI in include/ssamd.h and include/ssamd_active.h).
+"""ctypes binding of libssamd.so (C ABI in include/ssamd.h, include/ssamd_active.h and include/ssamd_graycode.h).
 
 This is the only place Python touches the native library.  There is no Python or
 CPU fallback for the operators: if the library is missing, or no HIP device is
@@ -21,6 +21,8 @@ if os.environ.get("SSAMD_LIB"):
     LIB_PATH = os.environ["SSAMD_LIB"]
 ABI_VERSION = 8
 ACTIVE_VERSION = 1         # SSAMD_ACTIVE_VERSION of include/ssamd_active.h, the second public header of the same library
+GRAYCODE_VERSION = 1       # SSAMD_GRAYCODE_VERSION of include/ssamd_graycode.h, the third
+GRAYCODE_BLOCK = 1024      # SSAMD_GRAYCODE_BLOCK: pixels per block of the decode counts and the offsets
 
 (K_LAB, K_ASW_AGG, K_ASW_FIN, K_GSW_AGG, K_GSW_FIN, K_REMAP, K_REPROJECT, K_ASW_ALT, K_ASW_EXACT, K_UNWRAP, K_FTP,
  K_NPUNWRAP, K_COUNT) = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12
@@ -63,6 +65,9 @@ _SIGNATURES = (
     ("iiiiiI", "ssamd_asw_geometry ssamd_asw_kernel_form ssamd_gsw_geometry"),
     ("ss", "ssamd_set_option"),
     ("isL", "ssamd_counter"),
+    # include/ssamd_graycode.h (SSAMD_GRAYCODE_VERSION); tests/test_graycode_cpu.py holds these rows to that header
+    ("piiipp" + 9 * "i" + "DipIi", "ssamd_graycode_cloud"),
+    ("piiiiDppp", "ssamd_graycode_cloud_device"),
 ) + tuple((args + last, name + suffix) for args, name in (       # NAME(..., int device) and NAME_device(..., void *stream)
     ("piiidp", "ssamd_iir_unwrap"),
     ("plllddp", "ssamd_np_unwrap"),
@@ -72,6 +77,8 @@ _SIGNATURES = (
     # include/ssamd_active.h (SSAMD_ACTIVE_VERSION); tests/test_stereo_ftp_cpu.py holds these rows to that header
     ("piiiiiipp", "ssamd_ftp_reference"),
     ("piiiip", "ssamd_stripe_centroids"),
+    ("piiipp" + 9 * "i" + "pp", "ssamd_graycode_decode"),
+    ("pip", "ssamd_graycode_offsets"),
 ) for last, suffix in (("i", ""), ("p", "_device")))
 _RETURN_STRING = ("ssamd_last_error", "ssamd_kernel_name")
 _CTYPES = {"i": ctypes.c_int, "l": ctypes.c_longlong, "d": ctypes.c_double, "f": ctypes.c_float, "p": ctypes.c_void_p,

@@ -5,7 +5,7 @@ Fourier-transform profilometry of ``simplestereo.active`` (reference ``simpleste
 frame in, point cloud out, and the steps it is made of -- the central stripe, the virtual reference image, the demodulation
 and the triangulation of the unwrapped phase -- each per-pixel step executed by one HIP kernel on an AMD MI355X through the C
 ABI of ``libssamd.so`` (``ssamd_ftp_phase``, ``ssamd_ftp_cloud``: ``include/ssamd.h``; ``ssamd_ftp_reference``,
-``ssamd_stripe_centroids``: ``include/ssamd_active.h``).  No cv2 call anywhere.
+``ssamd_stripe_centroids``: ``include/ssamd_active.h``) -- and Gray-code structured light, ``GrayCode``.  No cv2 call anywhere.
 
     import simplestereo_amd as ss
     ftp = ss.active.StereoFTP(rig, ss.active.buildFringe(period, stripeColor="r"), period)
@@ -17,6 +17,9 @@ ABI of ``libssamd.so`` (``ssamd_ftp_phase``, ``ssamd_ftp_cloud``: ``include/ssam
     phase = ss.active.ftpPhase(imgObj, imgRef, fc, unwrap="numpy")      # the reference's default unwrapping
     k = ss.active.ftpFringeOrder(phase, stripe_indexes, rig, z_plane, period, stripeCentralPeak)
     cloud = ss.active.ftpCloud(phase, rig, z_plane, period, k)         # float64 [H, W, 3], on the device if phase is
+
+    points = ss.active.GrayCode(rig).getCloud(images)                   # float64 (n, 1, 3); images uint8 [N, H, W] or paths
+    proj = ss.active.grayCodeDecode(images, rig.res2, white_thr=5)      # int32 [H, W, 2]: (xDec, yDec) or (-1, -1)
 
 ``ftpPhase`` is the demodulation of ``StereoFTP.getCloud`` (``active.py:675-737``; the same lines are
 ``StereoFTP_PhaseOnly.getPhase``, ``:2012-2074``): gray by the channel maximum, a row-wise FFT of the object image and of
@@ -41,7 +44,20 @@ centroids come to the host), ``_triangulate`` and ``_calculateCameraFrequency`` 
 ``fc``), ``ftpReference``, ``ftpPhase``, ``ftpFringeOrder``, ``ftpCloud``.  Where the reference calls cv2, OpenCV's published
 arithmetic is restated; parity with cv2 itself is pinned only where cv2 is installed (``tests/test_cv2_pins_ftp.py``): the
 bicubic weight table (``_rigs._cubic_table`` lists its choices), ``cv2.undistort``, the float32 roundings of
-``_calculateCameraFrequency``.  ``StereoFTPAnaglyph``, ``StereoFTP_Mapping``, ``StereoFTP_PhaseOnly`` and Gray code are not here.
+``_calculateCameraFrequency``.  ``StereoFTPAnaglyph``, ``StereoFTP_Mapping`` and ``StereoFTP_PhaseOnly`` are not here.
+
+``GrayCode`` (alias ``GrayCodeSingle``) is the reference's other structured-light method (``active.py:1130-1263``; C ABI in
+``include/ssamd_graycode.h``).  There ``getCloud`` calls ``cv2.structured_light_GrayCodePattern.getProjPixel`` once per camera
+pixel from a Python double loop; here three HIP kernels do the work: ``graycode_decode_kernel`` (``cv2.undistort`` of every
+pattern image fused in, ``getProjPixel`` for every pixel, valid pixels counted per block), ``graycode_scan_kernel`` (where each
+block's points start) and ``graycode_cloud_kernel`` (the triangulation ``ftpCloud`` ends with, by the same device function,
+written compacted in raster order, or dense with NaN).  ``grayCodeDecode`` is the decode on its own; ``grayCodePattern`` and
+``generateGrayCodeImgs`` make the pattern images.  OpenCV's published algorithm is restated (``tests/_graycode_ref.py``);
+parity with cv2 itself is pinned only where ``cv2.structured_light`` is installed (``tests/test_cv2_pins_graycode.py``).
+``roi`` is read as the reference's loops read it, ``range(roi_y, roi_h)`` and ``range(roi_x, roi_w)``: (x, y, x_end, y_end).
+``GrayCodeDouble`` stays out: the reference's version cannot run (it indexes a projector-shaped array with camera coordinates,
+adds 0.5 to an integer array in place and uses a ``self.R_inv`` it never defines); ``grayCodeDecode`` of the two cameras' stacks
+is the piece to write one's own from.
 
 The band is the reference's, decided exactly (numpy's mask on ``np.fft.fftfreq``); the phase is not bit-identical to
 numpy's pocketfft -- the kernel sums a band-limited direct DFT in another order -- but agrees with the exact angle to a few
@@ -101,10 +117,37 @@ no row of the frame holds a stripe                         ``ValueError("Central
 ``plot=True``                                              ``NotImplementedError``
 =========================================================  =======================
 
+``grayCodePattern``, ``generateGrayCodeImgs``, ``grayCodeDecode``, ``GrayCode`` and ``GrayCode.getCloud``:
+
+=========================================================  =======================
+condition                                                  exception
+=========================================================  =======================
+a resolution (``rig.res2`` too) that is not two integers   ``ValueError``
+in 1 .. 65536
+``images`` neither ndarray, CUDA/HIP tensor nor a list or  ``TypeError``
+tuple of ndarrays (of paths too for ``getCloud``), or not
+uint8
+``images`` not [M, Hc, Wc], a listed image not [Hc, Wc]    ``ValueError``
+fewer images than the projector has patterns               ``ValueError``
+``white_thr`` not an integer in 0 .. 256                   ``ValueError``
+``maps`` not a pair, a map not [Hc, Wc]                    ``ValueError``
+a map neither ndarray nor tensor, not float32, or on a     ``TypeError``
+device the images are not on
+``roi`` not four integers, a negative origin, or a         ``ValueError``
+non-empty region reaching outside the image
+``getCloud``: an image that is not of ``res1``             ``ValueError("Image size of {name or index} is mismatch!")``
+``getCloud``: a file that is not 8-bit single-channel      ``ValueError`` (pass arrays)
+``distCoeffs2`` with a tilted sensor (tauX, tauY)          ``NotImplementedError``
+PIL absent: ``generateGrayCodeImgs``, a list of paths      ``ImportError``
+=========================================================  =======================
+
 All of them are raised before any native call.  An image or a phase map with no rows or no columns gives an empty array;
-``findCentralStripe`` of such an image is ``None``.
+``findCentralStripe`` of such an image is ``None``; an empty ``roi`` gives ``(0, 1, 3)`` points.
 """
+import ctypes
+import math
 import numbers
+import os
 
 import numpy as np
 
@@ -113,9 +156,11 @@ from ._rigs import INTER_LINEAR, _dist_vector, _distort, _init_undistort_rectify
 from ._native import c_double as _c_double, is_device_tensor as _is_device_tensor
 
 __all__ = ["ftpPhase", "ftpCloud", "ftpFringeOrder", "ftpGeometry", "FtpGeometry", "MAX_WIDTH", "ftpReference",
-           "findCentralStripe", "buildFringe", "StereoFTP"]
+           "findCentralStripe", "buildFringe", "StereoFTP", "grayCodePattern", "generateGrayCodeImgs", "grayCodeDecode", "GrayCode",
+           "GrayCodeSingle", "MAX_PROJECTOR"]
 
 MAX_WIDTH = 8192          # SSAMD_FTP_MAX_W: twiddle table, gray rows and a chunk of bins of one row in 160 KiB of LDS
+MAX_PROJECTOR = 65536     # Gray code: at most 16 bits per projector axis, 64 pattern images
 
 
 def _number(v, what):
@@ -724,8 +769,7 @@ class StereoFTP:
 
     def _host_maps(self):
         if self._undistort_maps is None:
-            rig = self.stereoRig
-            self._undistort_maps = _init_undistort_rectify_map(rig.intrinsic1, rig.distCoeffs1, np.eye(3), rig.intrinsic1, rig.res1)
+            self._undistort_maps = _undistort_maps(self.stereoRig)
         return self._undistort_maps
 
     def _undistort(self, img):
@@ -860,3 +904,417 @@ class StereoFTP:
             phase = unwrappingMethod(ftpPhase(cut, imgRef, fc, radius_factor))
         k = ftpFringeOrder(phase, stripe_indexes, G, stripeCentralPeak=self.stripeCentralPeak)
         return ftpCloud(phase, G, k=k)
+
+
+# ------------------------------------------------------------------------------------------------ Gray code
+def _undistort_maps(rig):
+    """float32 (mapx, mapy) of ``cv2.undistort(img, K1, distCoeffs1)``: ``initUndistortRectifyMap(K1, D1, I, K1, res1)``"""
+    return _init_undistort_rectify_map(rig.intrinsic1, rig.distCoeffs1, np.eye(3), rig.intrinsic1, rig.res1)
+
+
+def _integer(v):
+    return isinstance(v, (numbers.Integral, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
+def _gray_bits(n):
+    """``ceil(log(double(n)) / log(2.0))`` as OpenCV computes it: the bits of a Gray code over ``n`` positions"""
+    return int(math.ceil(math.log(float(n)) / math.log(2.0)))
+
+
+def _proj_res(resolution):
+    """-> (width, height, ncol, nrow) of a projector"""
+    try:
+        vals = tuple(resolution)
+    except TypeError:
+        vals = ()
+    if len(vals) != 2 or not all(_integer(v) for v in vals) or not all(1 <= int(v) <= MAX_PROJECTOR for v in vals):
+        raise ValueError("the projector resolution must be (width, height), two integers in 1 .. %d" % MAX_PROJECTOR)
+    w, h = int(vals[0]), int(vals[1])
+    return w, h, _gray_bits(w), _gray_bits(h)
+
+
+def grayCodePattern(resolution):
+    """
+    The Gray-code pattern images of a projector: ``cv2.structured_light_GrayCodePattern.create(width, height).generate()``.
+
+    ``ncol = ceil(log(width) / log(2))`` column bits and ``nrow`` row bits likewise (in double, as OpenCV computes them);
+    ``N = 2 * ncol + 2 * nrow`` images.  The column images come first, most significant bit first: image ``2 * (ncol - 1 - k)``
+    holds bit k of ``j ^ (j >> 1)`` of column j as 0 / 255 and image ``2 * (ncol - 1 - k) + 1`` its inverse; the row images
+    follow from index ``2 * ncol`` in the same way for row i.  numpy on the host: O(N W H) once per rig.
+
+    Parameters
+    ----------
+    resolution : (width, height)
+        Of the projector, each 1 .. 65536.
+
+    Returns
+    -------
+    numpy.ndarray
+        uint8 ``[N, height, width]``.
+    """
+    w, h, ncol, nrow = _proj_res(resolution)
+    out = np.empty((2 * (ncol + nrow), h, w), np.uint8)
+    for first, nbits, length, along_x in ((0, ncol, w, True), (2 * ncol, nrow, h, False)):
+        j = np.arange(length, dtype=np.int64)
+        gray = j ^ (j >> 1)
+        for k in range(nbits):
+            line = (((gray >> k) & 1) * 255).astype(np.uint8)
+            line = line[None, :] if along_x else line[:, None]
+            out[first + 2 * (nbits - 1 - k)] = line
+            out[first + 2 * (nbits - 1 - k) + 1] = 255 - line
+    return out
+
+
+def generateGrayCodeImgs(targetDir, resolution):
+    """
+    Generate the Gray-code images and save them as PNG (the reference's ``generateGrayCodeImgs``, ``active.py:23-64``).
+
+    Writes ``0.png`` .. ``N-1.png`` (:func:`grayCodePattern`: each image is followed by its inverse, the vertical stripes come
+    first) and a ``black.png`` and a ``white.png`` for threshold calibration.  Written with PIL.
+
+    Parameters
+    ----------
+    targetDir : str
+        Directory to write to; created if it does not exist.
+    resolution : (width, height)
+        Of the projector.
+
+    Returns
+    -------
+    int
+        Number of patterns N (black and white not counted).
+    """
+    imgs = grayCodePattern(resolution)
+    try:
+        from PIL import Image
+    except ImportError:
+        raise ImportError("generateGrayCodeImgs writes PNG files with PIL (the pillow package), which is not installed") from None
+    if not os.path.exists(targetDir):
+        os.mkdir(targetDir)
+    for i in range(imgs.shape[0]):
+        Image.fromarray(imgs[i]).save(os.path.join(targetDir, str(i) + ".png"))
+    h, w = (int(resolution[1]), int(resolution[0]))
+    Image.fromarray(np.zeros((h, w), np.uint8)).save(os.path.join(targetDir, "black.png"))
+    Image.fromarray(np.full((h, w), 255, np.uint8)).save(os.path.join(targetDir, "white.png"))
+    return int(imgs.shape[0])
+
+
+def _gray_stack(images, size=None):
+    """-> (contiguous uint8 stack [M, Hc, Wc], is it on a device).  A sequence of [Hc, Wc] host arrays is stacked on the host;
+    with ``size = (width, height)`` every plane must be of that size (the reference's check and message, ``active.py:1205-1206``)."""
+    dev = _is_device_tensor(images)
+    if dev or isinstance(images, np.ndarray):
+        if dev:
+            import torch
+            if images.dtype != torch.uint8:
+                raise TypeError("images must be a uint8 tensor")
+        elif images.dtype != np.uint8:
+            raise TypeError("images must be a uint8 array")
+        if images.ndim != 3:
+            raise ValueError("images must be [M, Hc, Wc]: one gray image per pattern")
+        if size is not None and (int(images.shape[2]), int(images.shape[1])) != size:
+            raise ValueError("Image size of 0 is mismatch!")
+        return (images.contiguous() if dev else np.ascontiguousarray(images)), dev
+    if isinstance(images, (str, bytes)) or not isinstance(images, (list, tuple)):
+        raise TypeError("images must be a uint8 ndarray or CUDA/HIP tensor [M, Hc, Wc], or a sequence of [Hc, Wc] uint8 arrays")
+    planes = []
+    for i, img in enumerate(images):
+        if not isinstance(img, np.ndarray) or img.dtype != np.uint8:
+            raise TypeError("images[%d] must be a uint8 ndarray" % i)
+        if img.ndim != 2:
+            raise ValueError("images[%d] must be [Hc, Wc]: a gray image" % i)
+        if (size is not None and (img.shape[1], img.shape[0]) != size) or (planes and img.shape != planes[0].shape):
+            raise ValueError("Image size of %d is mismatch!" % i)
+        planes.append(img)
+    if not planes:
+        return np.empty((0,) + ((size[1], size[0]) if size is not None else (0, 0)), np.uint8), False
+    return np.ascontiguousarray(np.stack(planes)), False
+
+
+def _gray_roi(roi, res):
+    """-> (x, y, w, h) of the reference's loops ``range(roi_y, roi_h)`` / ``range(roi_x, roi_w)`` (``active.py:1221-1222``): the
+    third and fourth entry are exclusive END coordinates; empty (w or h 0) when an end does not lie beyond its origin"""
+    W, H = int(res[0]), int(res[1])
+    if roi is None:
+        return 0, 0, W, H
+    try:
+        vals = tuple(roi)
+    except TypeError:
+        vals = ()
+    if len(vals) != 4 or not all(_integer(v) for v in vals):
+        raise ValueError("roi must be four integers (x, y, x_end, y_end)")
+    x, y, xe, ye = (int(v) for v in vals)
+    if x < 0 or y < 0:
+        raise ValueError("roi %s starts outside the image" % ((x, y, xe, ye),))
+    w, h = max(xe - x, 0), max(ye - y, 0)
+    if w and h and (xe > W or ye > H):
+        raise ValueError("roi %s reaches outside the image (%d x %d)" % ((x, y, xe, ye), W, H))
+    return x, y, w, h
+
+
+def _white_thr(v):
+    if not _integer(v) or not 0 <= int(v) <= 256:
+        raise ValueError("white_thr must be an integer in 0 .. 256")
+    return int(v)
+
+
+def _gray_maps(maps, stack, dev):
+    """-> (mapx, mapy) like the stack (host arrays, or tensors on its device), or (None, None)"""
+    if maps is None:
+        return None, None
+    try:
+        mx, my = maps
+    except (TypeError, ValueError):
+        raise ValueError("maps must be (mapx, mapy)") from None
+    out = []
+    for m, name in ((mx, "mapx"), (my, "mapy")):
+        on_dev = _is_device_tensor(m)
+        if not (on_dev or isinstance(m, np.ndarray)):
+            raise TypeError("%s must be a float32 ndarray or CUDA/HIP tensor" % name)
+        if on_dev:
+            import torch
+            if m.dtype != torch.float32:
+                raise TypeError("%s must be float32" % name)
+            if not dev or m.device != stack.device:
+                raise TypeError("%s is on a device the images are not on" % name)
+            m = m.contiguous()
+        else:
+            if m.dtype != np.float32:
+                raise TypeError("%s must be float32" % name)
+            m = np.ascontiguousarray(m)
+        if tuple(m.shape) != tuple(stack.shape[1:]):
+            raise ValueError("%s must be [Hc, Wc] like the images, %s" % (name, tuple(stack.shape[1:])))
+        if dev and not on_dev:
+            import torch
+            m = torch.from_numpy(m).to(stack.device)
+        out.append(m)
+    return out[0], out[1]
+
+
+def _ptr(a):
+    return None if a is None else (a.data_ptr() if _is_device_tensor(a) else a.ctypes.data)
+
+
+def _gray_blocks(h, w):
+    return (h * w + _native.GRAYCODE_BLOCK - 1) // _native.GRAYCODE_BLOCK
+
+
+def _gray_decode_args(stack, proj, thr, mx, my, box):
+    x0, y0, w, h = box
+    pw, ph, ncol, nrow = proj
+    n = 2 * (ncol + nrow)
+    if int(stack.shape[0]) < n:
+        raise ValueError("a %d x %d projector needs %d pattern images, got %d" % (pw, ph, n, int(stack.shape[0])))
+    if h * w >= 1 << 31 or int(stack.shape[1]) * int(stack.shape[2]) >= 1 << 31:
+        raise ValueError("images or regions of 2^31 pixels or more are not supported")
+    return (_ptr(stack), n, int(stack.shape[1]), int(stack.shape[2]), _ptr(mx), _ptr(my), x0, y0, h, w, ncol, nrow, pw, ph, thr)
+
+
+def _gray_decode_device(stack, args, h, w):
+    """-> (decoded int32 [h, w, 2], valid pixels per block int32 [nblocks]) on the stack's device and current stream"""
+    import torch
+    out = torch.empty((h, w, 2), dtype=torch.int32, device=stack.device)
+    counts = torch.empty((_gray_blocks(h, w),), dtype=torch.int32, device=stack.device)
+    if h * w:
+        _native.call_on_stream(stack, _native.lib().ssamd_graycode_decode_device, *args, out.data_ptr(), counts.data_ptr(), invalid=_INVALID)
+    return out, counts
+
+
+def grayCodeDecode(images, projRes, white_thr=5, maps=None, roi=None):
+    """
+    Decode a stack of Gray-code images: ``cv2.structured_light_GrayCodePattern.getProjPixel`` for every pixel of the region,
+    by one HIP kernel (``graycode_decode_kernel``).
+
+    Per bit, with ``v1`` the pattern image and ``v2`` its inverse at the pixel: an error if ``|v1 - v2| < white_thr``; the Gray
+    bit is 1 if ``v1 > v2``, else 0 (so ``v1 == v2`` gives 0); Gray -> binary is the MSB-first prefix XOR; after both codes, an
+    error if ``xDec >= width or yDec >= height``.  ``black_thr`` plays no part in ``getProjPixel``.  A 1 x 1 projector has no
+    pattern images; every pixel then decodes to (0, 0) without error.  The piece to build a ``GrayCodeDouble`` of one's own from.
+
+    Parameters
+    ----------
+    images : ndarray or CUDA/HIP tensor uint8 ``[M, Hc, Wc]``, or a sequence of ``[Hc, Wc]`` uint8 arrays (stacked on the host)
+        In the order of :func:`grayCodePattern`.  ``M >= N``; only the first N are read (the reference ignores extra images).
+    projRes : (width, height)
+        Of the projector, each 1 .. 65536.
+    white_thr : int, optional
+        0 .. 256.  Default 5.
+    maps : (mapx, mapy), optional
+        float32 ``[Hc, Wc]``: every image is sampled as ``cv2.remap(img, mapx, mapy, INTER_LINEAR)`` samples it (1/32-pixel
+        fractions, ``(S + 512) >> 10``, border 0, non-finite coordinates 0) without the remapped images ever existing; the
+        result equals remapping every image with that arithmetic and decoding, value for value.  Default: the images as they are.
+    roi : (x, y, x_end, y_end), optional
+        The region ``[y, y_end) x [x, x_end)``, as :meth:`GrayCode.getCloud` reads it.  Default: the whole image.
+
+    Returns
+    -------
+    ndarray or tensor
+        int32 ``[h, w, 2]``: ``(xDec, yDec)``, or ``(-1, -1)`` where ``getProjPixel`` reports an error.  A tensor on the images'
+        device, computed on its current stream, for a tensor.
+    """
+    proj = _proj_res(projRes)
+    thr = _white_thr(white_thr)
+    stack, dev = _gray_stack(images)
+    mx, my = _gray_maps(maps, stack, dev)
+    box = _gray_roi(roi, (int(stack.shape[2]), int(stack.shape[1])))
+    args = _gray_decode_args(stack, proj, thr, mx, my, box)
+    h, w = box[3], box[2]
+    if dev:
+        return _gray_decode_device(stack, args, h, w)[0]
+    out = np.empty((h, w, 2), np.int32)
+    if h * w:
+        _native.check(_native.lib().ssamd_graycode_decode(*args, out.ctypes.data, None, -1), _INVALID)
+    return out
+
+
+class GrayCode:
+    """
+    Gray-code structured light with a calibrated camera-projector rig (the reference's ``GrayCode``, ``active.py:1130-1263``),
+    with no cv2 call: decode, compaction and triangulation are three HIP kernels.
+
+    Parameters
+    ----------
+    rig : StereoRig
+        Camera in position 1 (world origin), projector in position 2.  ``rig.distCoeffs2 = None`` ignores the projector's
+        distortion.
+    black_thr : int, optional
+        Stored; ``getProjPixel`` does not read it (it belongs to ``computeShadowMasks``).  Default 40.
+    white_thr : int, optional
+        Minimum difference between a pattern image and its inverse for a valid pixel, 0 .. 256.  Default 5.
+
+    The attributes are the reference's: ``rig``, ``num_patterns``, ``Rectify1``, ``Rectify2``, ``R_inv`` (4 x 4).  There is no
+    ``graycode`` attribute: no cv2 object exists.  The undistortion maps of the camera go to a device once per instance.
+    """
+
+    def __init__(self, rig, black_thr=40, white_thr=5):
+        self.rig = rig
+        self.black_thr = black_thr
+        self.white_thr = _white_thr(white_thr)
+        self._proj = _proj_res(rig.res2)
+        self.num_patterns = 2 * (self._proj[2] + self._proj[3])
+        self.Rectify1, self.Rectify2, commonR = _low_level_rectify(rig)
+        R_inv = np.linalg.inv(commonR)
+        R_inv = np.hstack((np.vstack((R_inv, np.zeros((1, 3)))), np.zeros((4, 1))))
+        R_inv[3, 3] = 1
+        self.R_inv = R_inv
+        self._undistort_maps = None      # float32 (mapx, mapy) of cv2.undistort, host
+        self._on_device = {}             # device -> (mapx, mapy) tensors
+
+    def _maps(self, device=None):
+        if self._undistort_maps is None:
+            self._undistort_maps = _undistort_maps(self.rig)
+        if device is None:
+            return self._undistort_maps
+        if str(device) not in self._on_device:
+            import torch
+            self._on_device[str(device)] = tuple(torch.from_numpy(m).to(device) for m in self._undistort_maps)
+        return self._on_device[str(device)]
+
+    def _geometry(self):
+        """The ``SSAMD_FTP_CLOUD_NGEOM`` doubles of ``ssamd_graycode_cloud``: only what the triangulation reads -- K2,
+        ``distCoeffs2``, the rectifying transforms, the inverse common orientation, the baseline.  Neither the epipole nor a
+        phase period is in it, so ``T[2] == 0`` is fine."""
+        rig = self.rig
+        dist = _dist_vector(rig.distCoeffs2)                      # NotImplementedError for a tilted sensor; None is no distortion
+        K2 = np.asarray(rig.intrinsic2, dtype=np.float64)
+        g = np.zeros(NGEOM)
+        g[12:16] = K2[0, 0], K2[1, 1], K2[0, 2], K2[1, 2]
+        g[16:28] = dist[:12]
+        g[28:37] = K2.ravel()
+        g[40:49] = self.Rectify1.ravel()
+        g[49:58] = self.Rectify2.ravel()
+        g[58:67] = self.R_inv[:3, :3].ravel()
+        g[67] = rig.getBaseline()
+        if not np.isfinite(g).all():
+            raise ValueError("the rig gives a geometry that is not finite")
+        return g
+
+    def _load(self, paths, size):
+        """The first ``num_patterns`` files as uint8 planes.  cv2's colour -> gray conversion is not restated: only 8-bit
+        single-channel files are read."""
+        try:
+            from PIL import Image
+        except ImportError:
+            raise ImportError("reading image files needs PIL (the pillow package), which is not installed: pass arrays") from None
+        planes = []
+        for fname in paths[:self.num_patterns]:
+            with Image.open(fname) as im:
+                if im.mode != "L":
+                    raise ValueError("%s is not an 8-bit single-channel image (mode %r): convert it yourself and pass arrays"
+                                     % (fname, im.mode))
+                img = np.array(im, dtype=np.uint8)
+            if (img.shape[1], img.shape[0]) != size:
+                raise ValueError("Image size of %s is mismatch!" % (fname,))
+            planes.append(img)
+        return planes
+
+    def getCloud(self, images, roi=None, dense=False):
+        """
+        The 3-D points of a set of Gray-code images (``active.py:1174-1263``).
+
+        The reference's steps: ``cv2.undistort`` of every image (here fused into the decode: the maps of
+        ``initUndistortRectifyMap(K1, D1, I, K1, res1)``, :func:`grayCodeDecode`), ``getProjPixel`` for every pixel of the roi,
+        and for the valid ones, from ``pc = (x + 0.5, y + 0.5)`` and ``pp = (xDec + 0.5, yDec + 0.5)``:
+        ``cv2.undistortPoints(pp, K2, distCoeffs2, P=K2)``, the two rectifying homographies, ``baseline / |disparity|`` and the
+        common rotation undone -- the operations that end :func:`ftpCloud`, by the same device function, fp64.
+
+        Parameters
+        ----------
+        images : what :func:`grayCodeDecode` takes, or a sequence of paths
+            Of the rig's ``res1``, in the order of the patterns; any following extra image is ignored (e.g. full white).
+            Paths are opened with PIL and must be 8-bit single-channel files.
+        roi : (x, y, x_end, y_end), optional
+            As the reference's loops read it, ``range(roi_y, roi_h)`` and ``range(roi_x, roi_w)``: the third and fourth entry are
+            exclusive end coordinates, not a width and a height.  Default None: the whole image.
+        dense : bool, optional
+            ``True`` (the reference's todo): the cloud in the shape of the roi with NaN at the invalid pixels; with a tensor
+            nothing is read back and the whole chain is asynchronous on the current stream.  Default False.
+
+        Returns
+        -------
+        ndarray or tensor
+            float64 ``(n, 1, 3)``, the points of the valid pixels in raster order -- or ``[h, w, 3]`` with ``dense``.  An
+            ndarray for host images, a tensor on the images' device for a tensor.
+        """
+        size = (int(self.rig.res1[0]), int(self.rig.res1[1]))
+        if isinstance(images, (list, tuple)) and len(images) and all(isinstance(p, (str, os.PathLike)) for p in images):
+            images = self._load(images, size)
+        stack, dev = _gray_stack(images, size)
+        box = _gray_roi(roi, size)
+        geom = self._geometry()
+        mx, my = self._maps(stack.device if dev else None)
+        args = _gray_decode_args(stack, self._proj, self.white_thr, mx, my, box)
+        x0, y0, w, h = box
+        lib = _native.lib()
+        if not dev:
+            buf = np.empty((h * w, 3), np.float64)
+            n = ctypes.c_int(0)
+            if h * w:
+                _native.check(lib.ssamd_graycode_cloud(*args, geom.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), 1 if dense else 0,
+                                                       buf.ctypes.data, ctypes.byref(n), -1), _INVALID)
+            if dense:
+                return buf.reshape(h, w, 3)
+            pts = buf[:n.value]
+            return (pts if n.value == h * w else pts.copy()).reshape(-1, 1, 3)
+        import torch
+        decoded, counts = _gray_decode_device(stack, args, h, w)
+        gp = geom.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        if dense:
+            out = torch.empty((h, w, 3), dtype=torch.float64, device=stack.device)
+            if h * w:
+                _native.call_on_stream(stack, lib.ssamd_graycode_cloud_device, decoded.data_ptr(), h, w, x0, y0, gp, None, out.data_ptr(),
+                                       invalid=_INVALID)
+            return out
+        if not h * w:
+            return torch.empty((0, 1, 3), dtype=torch.float64, device=stack.device)
+        offsets = torch.empty((counts.shape[0] + 1,), dtype=torch.int32, device=stack.device)
+        _native.call_on_stream(stack, lib.ssamd_graycode_offsets_device, counts.data_ptr(), int(counts.shape[0]), offsets.data_ptr(),
+                               invalid=_INVALID)
+        n = int(offsets[-1].item())                                # the one read-back: the number of points sizes the result
+        out = torch.empty((n, 1, 3), dtype=torch.float64, device=stack.device)
+        if n:
+            _native.call_on_stream(stack, lib.ssamd_graycode_cloud_device, decoded.data_ptr(), h, w, x0, y0, gp, offsets.data_ptr(),
+                                   out.data_ptr(), invalid=_INVALID)
+        return out
+
+
+GrayCodeSingle = GrayCode

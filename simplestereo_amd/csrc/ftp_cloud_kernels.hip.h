@@ -64,19 +64,16 @@ __device__ __forceinline__ void ftp_project(const Geom &G, double u, double v, d
     Ya = G.f2[1] * yd + G.f2[3];
 }
 
-// One pixel centre (u, v) and its unwrapped phase (already shifted by the fringe order) -> point o[0..2].
+// The camera pixel centre (u, v) and the projector point (Xh, Yh) it corresponds to -> point o[0..2]: the triangulation both
+// structured-light methods end with (active.py:813-841 for StereoFTP, :1246-1261 for GrayCode), the operations of
+// tests/_ftp_cloud_ref.py (cloud_from_geometry) from its undistort_points line to the end.  Reads f2, d, P, R1, R2, Ri and
+// baseline of G; ftp_cloud_kernel and graycode_cloud_kernel (graycode_kernels.hip.h) share this text.
 template <int MODEL>
-__device__ __forceinline__ void ftp_cloud_pixel(const FtpCloudGeom &G, double u, double v, double ph, double *o)
+__device__ __forceinline__ void ftp_triangulate(const FtpCloudGeom &G, double u, double v, double Xh, double Yh, double *o)
 {
 #pragma clang fp contract(off)
     const double k1 = G.d[0], k2 = G.d[1], p1 = G.d[2], p2 = G.d[3], k3 = G.d[4], k4 = G.d[5], k5 = G.d[6], k6 = G.d[7];
     const double s1 = G.d[8], s2 = G.d[9], s3 = G.d[10], s4 = G.d[11];
-    // projector coordinates of the camera pixel on the reference plane: projectPoints
-    double Xa, Ya;
-    ftp_project<MODEL>(G, u, v, Xa, Ya);
-    // phase -> projector column, row on the epipolar line
-    const double Xh = Xa + ph / G.two_pi_fp;
-    const double Yh = ((Xh - G.ep[0]) / (Xa - G.ep[0])) * (Ya - G.ep[1]) + G.ep[1];
     // undistortPoints(H, K2, dist2, P = K2): five fixed-point iterations
     const double xn = (Xh - G.f2[2]) / G.f2[0], yn = (Yh - G.f2[3]) / G.f2[1];
     double a = xn, b = yn;
@@ -108,6 +105,20 @@ __device__ __forceinline__ void ftp_cloud_pixel(const FtpCloudGeom &G, double u,
     o[0] = (G.Ri[0] * px + G.Ri[1] * py) + G.Ri[2] * pz;
     o[1] = (G.Ri[3] * px + G.Ri[4] * py) + G.Ri[5] * pz;
     o[2] = (G.Ri[6] * px + G.Ri[7] * py) + G.Ri[8] * pz;
+}
+
+// One pixel centre (u, v) and its unwrapped phase (already shifted by the fringe order) -> point o[0..2].
+template <int MODEL>
+__device__ __forceinline__ void ftp_cloud_pixel(const FtpCloudGeom &G, double u, double v, double ph, double *o)
+{
+#pragma clang fp contract(off)
+    // projector coordinates of the camera pixel on the reference plane: projectPoints
+    double Xa, Ya;
+    ftp_project<MODEL>(G, u, v, Xa, Ya);
+    // phase -> projector column, row on the epipolar line
+    const double Xh = Xa + ph / G.two_pi_fp;
+    const double Yh = ((Xh - G.ep[0]) / (Xa - G.ep[0])) * (Ya - G.ep[1]) + G.ep[1];
+    ftp_triangulate<MODEL>(G, u, v, Xh, Yh, o);
 }
 
 // phase [h][w] (ROI origin x0, y0 in the camera image) -> out [h][w][3].  Pixels are one flattened index (npix = h w < 2^31):
