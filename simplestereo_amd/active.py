@@ -5,7 +5,8 @@ Fourier-transform profilometry of ``simplestereo.active`` (reference ``simpleste
 frame in, point cloud out, and the steps it is made of -- the central stripe, the virtual reference image, the demodulation
 and the triangulation of the unwrapped phase -- each per-pixel step executed by one HIP kernel on an AMD MI355X through the C
 ABI of ``libssamd.so`` (``ssamd_ftp_phase``, ``ssamd_ftp_cloud``: ``include/ssamd.h``; ``ssamd_ftp_reference``,
-``ssamd_stripe_centroids``: ``include/ssamd_active.h``) -- and Gray-code structured light, ``GrayCode``.  No cv2 call anywhere.
+``ssamd_stripe_centroids``: ``include/ssamd_active.h``; ``ssamd_ftp_carrier_phase``, ``ssamd_ftp_mapping_cloud``:
+``include/ssamd_ftp_mapping.h``) -- and Gray-code structured light, ``GrayCode``.  No cv2 call anywhere.
 
     import simplestereo_amd as ss
     ftp = ss.active.StereoFTP(rig, ss.active.buildFringe(period, stripeColor="r"), period)
@@ -17,6 +18,12 @@ ABI of ``libssamd.so`` (``ssamd_ftp_phase``, ``ssamd_ftp_cloud``: ``include/ssam
     phase = ss.active.ftpPhase(imgObj, imgRef, fc, unwrap="numpy")      # the reference's default unwrapping
     k = ss.active.ftpFringeOrder(phase, stripe_indexes, rig, z_plane, period, stripeCentralPeak)
     cloud = ss.active.ftpCloud(phase, rig, z_plane, period, k)         # float64 [H, W, 3], on the device if phase is
+
+    cloud = ss.active.StereoFTP_Mapping(rig, fringe, period).getCloud(imgObj)       # no reference plane
+    phase = ss.active.ftpCarrierPhase(imgObj, fc, unwrap="numpy")       # the phase of one image, carrier included
+    theta = ss.active.ftpStripePhase(phase, stripe)                     # float: its mean along the stripe, bilinear
+    cloud = ss.active.ftpMappingCloud(phase, rig, period, stripeCentralPeak, theta)
+    phase, ph_obj, ph_ref = ss.active.StereoFTP_PhaseOnly(rig, fringe, period).getPhase(imgObj)
 
     points = ss.active.GrayCode(rig).getCloud(images)                   # float64 (n, 1, 3); images uint8 [N, H, W] or paths
     proj = ss.active.grayCodeDecode(images, rig.res2, white_thr=5)      # int32 [H, W, 2]: (xDec, yDec) or (-1, -1)
@@ -44,7 +51,16 @@ centroids come to the host), ``_triangulate`` and ``_calculateCameraFrequency`` 
 ``fc``), ``ftpReference``, ``ftpPhase``, ``ftpFringeOrder``, ``ftpCloud``.  Where the reference calls cv2, OpenCV's published
 arithmetic is restated; parity with cv2 itself is pinned only where cv2 is installed (``tests/test_cv2_pins_ftp.py``): the
 bicubic weight table (``_rigs._cubic_table`` lists its choices), ``cv2.undistort``, the float32 roundings of
-``_calculateCameraFrequency``.  ``StereoFTPAnaglyph``, ``StereoFTP_Mapping`` and ``StereoFTP_PhaseOnly`` are not here.
+``_calculateCameraFrequency``.
+
+``StereoFTP_Mapping`` is the classic method without a reference plane (``active.py:1266-1450``; C ABI in
+``include/ssamd_ftp_mapping.h``): ``ftpCarrierPhase`` (``np.angle(ifft(bandpass(fft(gray))))`` of the object image alone, the
+one-image form of ``ftpPhase``'s kernel), ``ftpStripePhase`` (the phase at the central stripe, ``map_coordinates`` restated on
+the host) and ``ftpMappingCloud`` (phase to projector column, the epipolar line of the fundamental matrix and the triangulation
+``ftpCloud`` ends with, per pixel in one kernel; ``ftpMappingGeometry`` packs what it reads).  ``StereoFTP_PhaseOnly.getPhase``
+(``:1950-2074``) returns the three wrapped maps of the demodulation.  ``StereoFTPAnaglyph`` stays out: its ``convertGrayscale``
+makes a float64 fringe, which takes ``cv2.remap(INTER_CUBIC)`` down OpenCV's floating-point path, and the reference marks the
+class as work in progress.
 
 ``GrayCode`` (alias ``GrayCodeSingle``) is the reference's other structured-light method (``active.py:1130-1263``; C ABI in
 ``include/ssamd_graycode.h``).  There ``getCloud`` calls ``cv2.structured_light_GrayCodePattern.getProjPixel`` once per camera
@@ -117,6 +133,26 @@ no row of the frame holds a stripe                         ``ValueError("Central
 ``plot=True``                                              ``NotImplementedError``
 =========================================================  =======================
 
+``ftpCarrierPhase`` raises what ``ftpPhase`` raises (first table); ``StereoFTP_Mapping.getCloud`` and
+``StereoFTP_PhaseOnly.getPhase`` what ``StereoFTP.getCloud`` raises.  ``ftpStripePhase``, ``ftpMappingGeometry`` and
+``ftpMappingCloud``:
+
+=========================================================  =======================
+condition                                                  exception
+=========================================================  =======================
+the phase neither ndarray nor CUDA/HIP tensor, or not      ``TypeError``
+float64
+the phase not [H, W], without pixels (``ftpStripePhase``)  ``ValueError``
+or (W, H) not the ``roi``'s (``ftpMappingCloud``)
+``stripe`` not a finite float array [n >= 1, 2]            ``ValueError``
+``roi`` not four non-negative integers inside ``res1``     ``ValueError``
+``period``, ``stripeCentralPeak`` or ``theta_shift`` not   ``ValueError``
+a finite number, or ``period == 0``
+``distCoeffs2`` with a tilted sensor (tauX, tauY)          ``NotImplementedError``
+an ``ftpGeometry`` result in place of the rig, or a        ``ValueError``
+packed geometry together with ``period`` or ``roi``
+=========================================================  =======================
+
 ``grayCodePattern``, ``generateGrayCodeImgs``, ``grayCodeDecode``, ``GrayCode`` and ``GrayCode.getCloud``:
 
 =========================================================  =======================
@@ -157,7 +193,8 @@ from ._native import c_double as _c_double, is_device_tensor as _is_device_tenso
 
 __all__ = ["ftpPhase", "ftpCloud", "ftpFringeOrder", "ftpGeometry", "FtpGeometry", "MAX_WIDTH", "ftpReference",
            "findCentralStripe", "buildFringe", "StereoFTP", "grayCodePattern", "generateGrayCodeImgs", "grayCodeDecode", "GrayCode",
-           "GrayCodeSingle", "MAX_PROJECTOR"]
+           "GrayCodeSingle", "MAX_PROJECTOR", "ftpCarrierPhase", "ftpStripePhase", "ftpMappingCloud", "ftpMappingGeometry",
+           "FtpMappingGeometry", "StereoFTP_Mapping", "StereoFTP_PhaseOnly"]
 
 MAX_WIDTH = 8192          # SSAMD_FTP_MAX_W: twiddle table, gray rows and a chunk of bins of one row in 160 KiB of LDS
 MAX_PROJECTOR = 65536     # Gray code: at most 16 bits per projector axis, 64 pattern images
@@ -212,6 +249,20 @@ def _band(fc, radius_factor, h):
 _INVALID = (_native.EINVAL, _native.ELIMIT)
 
 
+def _unwrap_mode(unwrap, tau, w):
+    """The checks ``ftpPhase`` and ``ftpCarrierPhase`` end with -> (the library's ``unwrap`` code, tau)"""
+    if unwrap is not None and not (isinstance(unwrap, str) and unwrap in ("iir", "numpy")):
+        raise ValueError('unwrap must be None, "iir" or "numpy"')
+    t = 1.0
+    if unwrap == "iir":
+        t = _c_double(tau)
+        if t < 0 or t > 1:
+            raise ValueError("Wrong tau value!")
+    if w > MAX_WIDTH:
+        raise ValueError("rows wider than %d columns are not supported (width %d)" % (MAX_WIDTH, w))
+    return {None: 0, "iir": 1, "numpy": 2}[unwrap], t
+
+
 def ftpPhase(imgObj, imgRef, fc, radius_factor=0.5, unwrap=None, tau=1):
     """
     Phase of a fringe image against a reference fringe image by Fourier-transform profilometry.
@@ -256,18 +307,38 @@ def ftpPhase(imgObj, imgRef, fc, radius_factor=0.5, unwrap=None, tau=1):
     if (h, w) != (h2, w2):
         raise ValueError("imgObj and imgRef must have the same height and width (%dx%d, %dx%d)" % (h, w, h2, w2))
     fmin, fmax = _band(fc, radius_factor, h)
-    if unwrap is not None and not (isinstance(unwrap, str) and unwrap in ("iir", "numpy")):
-        raise ValueError('unwrap must be None, "iir" or "numpy"')
-    t = 1.0
-    if unwrap == "iir":
-        t = _c_double(tau)
-        if t < 0 or t > 1:
-            raise ValueError("Wrong tau value!")
-    if w > MAX_WIDTH:
-        raise ValueError("rows wider than %d columns are not supported (width %d)" % (MAX_WIDTH, w))
-    uw = {None: 0, "iir": 1, "numpy": 2}[unwrap]
+    uw, t = _unwrap_mode(unwrap, tau, w)
     return _native.run("ssamd_ftp_phase", (obj, ref), (h, w),
                        lambda o, r, out: (o, ch_obj, r, ch_ref, h, w, fmin.ctypes.data, fmax.ctypes.data, uw, t, out), _INVALID)
+
+
+def ftpCarrierPhase(img, fc, radius_factor=0.5, unwrap=None, tau=1):
+    """
+    Phase of one fringe image by Fourier-transform profilometry: ``np.angle(ifft(bandpass(fft(gray))))``.
+
+    The demodulation of the reference's ``StereoFTP_Mapping.getCloud`` (``active.py:1354-1401``) and the second and third
+    result of ``StereoFTP_PhaseOnly.getPhase`` (``:2067-2074``): :func:`ftpPhase` without a reference image -- the same
+    band, the same band-limited direct DFT in fp64 (``ftp_carrier_kernel``), the angle of ``ghat`` itself.  The carrier is
+    still in it: along a row the phase grows by about ``2 * pi * fc`` per pixel, so it is the unwrapped map that is of use.
+
+    Parameters
+    ----------
+    img : ndarray or CUDA/HIP tensor, uint8
+        ``[H, W]`` gray or ``[H, W, 3]`` BGR (reduced by the channel maximum, the reference's ``convertGrayscale``).
+    fc, radius_factor, unwrap, tau
+        As in :func:`ftpPhase`.
+
+    Returns
+    -------
+    ndarray or tensor
+        float64 ``[H, W]``: a new array, or a tensor on the image's device computed on its current stream.  A row whose band
+        holds no bin is 0.0.
+    """
+    src, h, w, ch = _image(img, "img")
+    fmin, fmax = _band(fc, radius_factor, h)
+    uw, t = _unwrap_mode(unwrap, tau, w)
+    return _native.run("ssamd_ftp_carrier_phase", (src,), (h, w),
+                       lambda i, out: (i, ch, h, w, fmin.ctypes.data, fmax.ctypes.data, uw, t, out), _INVALID)
 
 
 # ------------------------------------------------------------------------------------------------ phase -> point cloud
@@ -904,6 +975,246 @@ class StereoFTP:
             phase = unwrappingMethod(ftpPhase(cut, imgRef, fc, radius_factor))
         k = ftpFringeOrder(phase, stripe_indexes, G, stripeCentralPeak=self.stripeCentralPeak)
         return ftpCloud(phase, G, k=k)
+
+
+# ------------------------------------------------------------------------------------------------ FTP without a reference plane
+def ftpStripePhase(phaseUnwrapped, stripe):
+    """
+    Mean of the phase map along the central stripe, sampled bilinearly: ``theta_shift`` of ``StereoFTP_Mapping.getCloud``
+    (``active.py:1431-1432``), ``np.mean(scipy.ndimage.map_coordinates(phase, (y, x), order=1))``.
+
+    scipy's linear spline with ``mode='constant'`` restated in numpy on the 4 n neighbours: with ``i = floor(c)`` and
+    ``t = c - i`` on each axis, ``((1-ty)(1-tx)) v00 + ((1-ty) tx) v01 + (ty (1-tx)) v10 + (ty tx) v11``; a point strictly
+    outside ``[0, n - 1]`` on either axis contributes 0.0.  O(H) work on the host; of a device map the 4 n neighbours are
+    read with one indexed read and one small copy.
+
+    Parameters
+    ----------
+    phaseUnwrapped : ndarray or CUDA/HIP tensor, float64 ``[H, W]``
+    stripe : float array ``[n >= 1, 2]``
+        (x, y) of the stripe in the coordinates of the map's array indexes, as :func:`findCentralStripe` returns them
+        (row ``r`` has ``y = r + 0.5``: the reference samples there).
+
+    Returns
+    -------
+    float
+    """
+    dev = _is_device_tensor(phaseUnwrapped)
+    h, w = _phase_dims(phaseUnwrapped)
+    try:
+        pts = np.asarray(stripe, dtype=np.float64)
+    except (TypeError, ValueError):
+        pts = np.zeros(0)
+    if pts.ndim != 2 or pts.shape[1] != 2 or pts.shape[0] < 1 or not np.isfinite(pts).all():
+        raise ValueError("stripe must be a finite float array [n >= 1, 2] of (x, y)")
+    if h == 0 or w == 0:
+        raise ValueError("phaseUnwrapped has no pixels")
+    x, y = pts[:, 0], pts[:, 1]
+    inside = (x >= 0) & (x <= w - 1) & (y >= 0) & (y <= h - 1)
+    xc, yc = np.where(inside, x, 0.0), np.where(inside, y, 0.0)
+    fx, fy = np.floor(xc), np.floor(yc)
+    tx, ty = xc - fx, yc - fy
+    ix0, iy0 = fx.astype(np.int64), fy.astype(np.int64)
+    ix1, iy1 = np.minimum(ix0 + 1, w - 1), np.minimum(iy0 + 1, h - 1)          # (weight 0 where clipped)
+    rows, cols = np.stack([iy0, iy0, iy1, iy1]), np.stack([ix0, ix1, ix0, ix1])
+    if dev:
+        import torch
+        v = phaseUnwrapped[torch.from_numpy(rows).to(phaseUnwrapped.device), torch.from_numpy(cols).to(phaseUnwrapped.device)].cpu().numpy()
+    else:
+        v = phaseUnwrapped[rows, cols]
+    val = ((((1 - ty) * (1 - tx)) * v[0] + ((1 - ty) * tx) * v[1]) + (ty * (1 - tx)) * v[2]) + (ty * tx) * v[3]
+    return float(np.mean(np.where(inside, val, 0.0)))
+
+
+def _phase_dims(phase):
+    """(H, W) of a float64 [H, W] array or device tensor"""
+    dev = _is_device_tensor(phase)
+    if not (dev or isinstance(phase, np.ndarray)):
+        raise TypeError("phaseUnwrapped must be a float64 ndarray or a CUDA/HIP torch.float64 tensor")
+    if dev:
+        import torch
+        if phase.dtype != torch.float64:
+            raise TypeError("phaseUnwrapped must be a float64 tensor")
+    elif phase.dtype != np.float64:
+        raise TypeError("phaseUnwrapped must be a float64 array")
+    if phase.ndim != 2:
+        raise ValueError("phaseUnwrapped must be [H, W]")
+    return int(phase.shape[0]), int(phase.shape[1])
+
+
+class FtpMappingGeometry(FtpGeometry):
+    """What ``ftpMappingCloud`` reads from a rig and a fringe period: ``geom`` (the ``SSAMD_FTP_CLOUD_NGEOM`` doubles with
+    only the triangulation's entries and ``2 pi fp`` filled in), ``F`` (float64 [9], the fundamental matrix row by row) and
+    ``roi = (x, y, w, h)``."""
+    __slots__ = ("F",)
+
+    def __init__(self, geom, roi, fp, F):
+        super().__init__(geom, roi, fp)
+        self.F = F
+
+
+def ftpMappingGeometry(rig, period, roi=None):
+    """
+    Pack the geometry of :func:`ftpMappingCloud`: build it once per rig and pass it in place of ``rig``.
+
+    What ``GrayCode`` packs -- K2, ``distCoeffs2``, the rectifying transforms and the common orientation of
+    ``_lowLevelRectify``, its inverse, ``rig.getBaseline()`` -- plus ``2 * pi * fp`` with ``fp = 1 / period`` and
+    ``rig.getFundamentalMatrix()``.  No reference plane and no epipole: a rig with ``T[2] == 0`` is fine.
+
+    Returns
+    -------
+    FtpMappingGeometry
+        ``.geom`` float64 [68], ``.F`` float64 [9], ``.roi`` (x, y, width, height).
+    """
+    per = _finite(period, "period")
+    if per == 0:
+        raise ValueError("period must not be 0")
+    box = _roi(roi, rig.res1)
+    dist = _dist_vector(rig.distCoeffs2)                      # NotImplementedError for a tilted sensor
+    K2 = np.asarray(rig.intrinsic2, dtype=np.float64)
+    rect1, rect2, common = _low_level_rectify(rig)
+    fp = 1 / per
+    g = np.zeros(NGEOM)
+    g[12:16] = K2[0, 0], K2[1, 1], K2[0, 2], K2[1, 2]
+    g[16:28] = dist[:12]
+    g[28:37] = K2.ravel()
+    g[39] = 2 * np.pi * fp
+    g[40:49] = rect1.ravel()
+    g[49:58] = rect2.ravel()
+    g[58:67] = np.linalg.inv(common).ravel()
+    g[67] = rig.getBaseline()
+    F = np.ascontiguousarray(np.asarray(rig.getFundamentalMatrix(), dtype=np.float64).reshape(9))
+    if not (np.isfinite(g).all() and np.isfinite(F).all()):
+        raise ValueError("the rig and period give a geometry that is not finite")
+    return FtpMappingGeometry(g, box, fp, F)
+
+
+def ftpMappingCloud(phaseUnwrapped, rig, period=None, stripeCentralPeak=None, theta_shift=0.0, roi=None):
+    """
+    Point cloud of the unwrapped phase of an object image alone: the per-pixel ``_triangulate`` that ends the reference's
+    ``StereoFTP_Mapping.getCloud`` (``active.py:1436-1447`` with ``:561-605``).
+
+    For every camera pixel centre ``(x + 0.5, y + 0.5)`` (plus the roi origin): the projector column
+    ``(phase - theta_shift) / (2 pi fp) + stripeCentralPeak + 0.5``, the projector row on the pixel's epipolar line (the
+    fundamental matrix), ``cv2.undistortPoints`` with ``P = K2`` (five iterations), the two rectifying homographies,
+    ``baseline / |disparity|`` and the common rotation undone.  One HIP kernel, fp64 throughout (``ftp_mapping_cloud_kernel``),
+    ending with the device function ``ftpCloud`` and ``GrayCode`` end with.  Not bit-identical to cv2 (another operation
+    order); equal bit for bit to the numpy restatement ``tests/_ftp_mapping_ref.py``.
+
+    Parameters
+    ----------
+    phaseUnwrapped : ndarray or CUDA/HIP tensor, float64 ``[H, W]``
+        A tensor is made contiguous and the work goes on its device's current stream.
+    rig : StereoRig
+        Camera in position 1, projector in position 2 -- or an :func:`ftpMappingGeometry` result, with ``period`` and ``roi``
+        left ``None``.
+    period : float
+        Fringe period on the projector image, in pixels.
+    stripeCentralPeak : float
+        Column of the central stripe's peak on the projector image.
+    theta_shift : float, optional
+        The phase at the central stripe (:func:`ftpStripePhase`), subtracted from the map.  Default 0.0.
+    roi : (x, y, width, height), optional
+        Region of the camera image the map covers; (width, height) must be the map's.  Default: the whole ``rig.res1``.
+
+    Returns
+    -------
+    ndarray or tensor
+        float64 ``[H, W, 3]`` in the camera's coordinate system.  A pixel with a non-finite phase holds the non-finite values
+        the formulas give there.
+    """
+    if isinstance(rig, FtpMappingGeometry):
+        if period is not None or roi is not None:
+            raise ValueError("with a packed geometry in place of the rig, period and roi are the geometry's: pass None")
+        G = rig
+    elif isinstance(rig, FtpGeometry):
+        raise ValueError("ftpMappingCloud takes the geometry of ftpMappingGeometry, not ftpGeometry's")
+    else:
+        G = ftpMappingGeometry(rig, period, roi)
+    peak = _finite(stripeCentralPeak, "stripeCentralPeak")
+    theta = _finite(theta_shift, "theta_shift")
+    phase, dev = _phase_map(phaseUnwrapped, G.roi)
+    x0, y0, w, h = G.roi
+    if dev:
+        phase = phase.contiguous()
+        if phase.data_ptr() % 16:
+            phase = phase.clone()     # a view at an odd storage offset: the kernel reads two phases per 16-byte load
+    gp, Fp = (a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) for a in (G.geom, G.F))
+    return _native.run("ssamd_ftp_mapping_cloud", (phase,), (h, w, 3), lambda src, out: (src, h, w, x0, y0, gp, Fp, theta, peak, out), _INVALID)
+
+
+class StereoFTP_Mapping(StereoFTP):
+    """
+    Classic Fourier Transform Profilometry (the reference's ``StereoFTP_Mapping``, ``active.py:1266-1450``): no virtual
+    reference plane; the phase of the object image alone is mapped to a projector column and every pixel is triangulated
+    through the fundamental matrix.  Constructor and attributes are :class:`StereoFTP`'s.
+    """
+
+    def getCloud(self, imgObj, radius_factor=0.5, roi=None, unwrappingMethod=None, plot=False):
+        """
+        Process a camera frame and get the point cloud (``active.py:1288-1450``).
+
+        The reference's steps in its order: ``cv2.undistort`` of the frame and the roi cut, :func:`findCentralStripe`,
+        ``_triangulate`` of the stripe, ``_calculateCameraFrequency`` -> ``fc``, :func:`ftpCarrierPhase` unwrapped
+        (``np.unwrap`` along x, then y, or ``unwrappingMethod`` of the wrapped map), :func:`ftpStripePhase`,
+        :func:`ftpMappingCloud`.  With a device tensor the frame, the phase and the cloud stay on the device: what crosses to
+        the host are the H stripe centroids and the 4 H phase values around the stripe.
+
+        With a ``roi`` whose origin is not (0, 0) the reference's ``_triangulate`` adds the roi offset to the stripe in
+        place, so its ``map_coordinates`` then samples the cut phase map at shifted coordinates; here the stripe is sampled
+        where it is.
+
+        Parameters and result as :meth:`StereoFTP.getCloud`.
+        """
+        if plot:
+            raise NotImplementedError("plot=True needs cv2 windows and matplotlib, which this package does not use")
+        cut, box, stripe, _ = self._frame(imgObj, roi)
+        stripe_world = self._triangulate(stripe, self.stripeCentralPeak, box)
+        fc = self._calculateCameraFrequency(stripe_world)
+        if unwrappingMethod is None:
+            phase = ftpCarrierPhase(cut, fc, radius_factor, unwrap="numpy")
+        else:
+            phase = unwrappingMethod(ftpCarrierPhase(cut, fc, radius_factor))
+        theta_shift = ftpStripePhase(phase, stripe)
+        G = ftpMappingGeometry(self.stereoRig, self.period, box)
+        return ftpMappingCloud(phase, G, stripeCentralPeak=self.stripeCentralPeak, theta_shift=theta_shift)
+
+
+class StereoFTP_PhaseOnly(StereoFTP):
+    """
+    The demodulation of :class:`StereoFTP` on its own (the reference's ``StereoFTP_PhaseOnly``, ``active.py:1453-2074``): the
+    wrapped phase against the virtual reference plane, and the wrapped phases of the object and of the reference image.
+    Constructor and attributes are :class:`StereoFTP`'s.
+    """
+
+    def getPhase(self, imgObj, radius_factor=0.5, roi=None, plot=False):
+        """
+        Process a camera frame and get its phase (``active.py:1950-2074``).
+
+        The reference's steps in its order: ``cv2.undistort`` of the frame and the roi cut, :func:`findCentralStripe`, the
+        stripe through ``cv2.undistortPoints(K1, distCoeffs1, P=K1)`` once more (as the reference does), ``_triangulate``,
+        ``_calculateCameraFrequency`` -> ``fc``, ``z_plane`` = the smallest stripe depth, :func:`ftpReference`,
+        :func:`ftpPhase` and :func:`ftpCarrierPhase` of the frame and of the reference image.  ``roi=None`` is the whole frame
+        (an ``UnboundLocalError`` in the reference); a frame without stripe is ``ValueError`` (``AttributeError`` there).
+
+        Returns
+        -------
+        tuple of three ndarrays or tensors, float64 ``[height, width]``, all wrapped
+            ``angle(ghat * conj(g0hat))``, ``angle(ghat)``, ``angle(g0hat)``.
+        """
+        if plot:
+            raise NotImplementedError("plot=True needs cv2 windows and matplotlib, which this package does not use")
+        cut, box, stripe, _ = self._frame(imgObj, roi)
+        rig = self.stereoRig
+        stripe_cam = _undistort_points(stripe, rig.intrinsic1, rig.distCoeffs1, R=rig.intrinsic1)
+        stripe_world = self._triangulate(stripe_cam, self.stripeCentralPeak, box)
+        fc = self._calculateCameraFrequency(stripe_world)
+        z_plane = np.min(stripe_world[:, 2])
+        G = ftpGeometry(rig, z_plane, self.period, box)
+        fringe = self._device_state(cut.device)[0] if _is_device_tensor(cut) else self.fringe
+        imgRef = ftpReference(fringe, G)
+        return (ftpPhase(cut, imgRef, fc, radius_factor), ftpCarrierPhase(cut, fc, radius_factor),
+                ftpCarrierPhase(imgRef, fc, radius_factor))
 
 
 # ------------------------------------------------------------------------------------------------ Gray code

@@ -171,4 +171,103 @@ __global__ __launch_bounds__(1024) void ftp_phase_kernel(const uint8_t *__restri
     }
 }
 
+// Wrapped phase of ONE fringe image, np.angle(ifft(bandpass(fft(gray)))): the demodulation of the reference's
+// StereoFTP_Mapping.getCloud (active.py:1354-1401) and the second and third result of StereoFTP_PhaseOnly.getPhase (:2067-2074).
+// ftp_phase_kernel with one image: the same band, table, lane groups and running indexes, half the accumulators, and the angle of
+// ghat itself as the epilogue.  A kernel of its own, so that the pair kernel's code object stays what it was.
+// LDS (dynamic):  double2 tw[w] | double2 bins[FTP_BIN_CHUNK] (G re, im) | uint8 gray[w]      (ftp_carrier_lds_bytes, ftp_plan.h)
+template <int CPT>
+__global__ __launch_bounds__(1024) void ftp_carrier_kernel(const uint8_t *__restrict__ img, int ch, int w, const int2 *__restrict__ band,
+                                                           const double2 *__restrict__ tw_g, int lanes_per_bin, int bin_chunk,
+                                                           double *__restrict__ out)
+{
+    extern __shared__ double2 ftp_lds[];
+    double2 *tw = ftp_lds;
+    double2 *bins = ftp_lds + w;
+    uint8_t *gray = reinterpret_cast<uint8_t *>(bins + bin_chunk);
+    const int T = blockDim.x, tid = threadIdx.x;
+    const size_t row = blockIdx.x;
+    double *orow = out + row * (size_t)w;
+    const int2 bd = band[row];
+    const int K = bd.y - bd.x + 1;
+    if (K <= 0) {                                        // np.angle(0j): exactly 0.0
+        for (int x = tid; x < w; x += T) orow[x] = 0.0;
+        return;
+    }
+
+    const uint8_t *prow = img + row * (size_t)w * ch;
+    for (int x = tid; x < w; x += T) {
+        tw[x] = tw_g[x];
+        gray[x] = ftp_gray(prow, ch, x);
+    }
+
+    // columns of this thread and their running index (s x) mod w, started at s = slo
+    const int sm0 = bd.x < 0 ? bd.x + w : bd.x;          // slo mod w
+    int xs[CPT], js[CPT];
+    double ar[CPT], ai[CPT];
+#pragma unroll
+    for (int c = 0; c < CPT; ++c) {
+        const int x = tid + c * T;
+        xs[c] = x < w ? x : 0;                           // columns past the row idle on tw[0]
+        js[c] = (int)(((long long)sm0 * xs[c]) % w);
+        ar[c] = ai[c] = 0.0;
+    }
+    const int Q = lanes_per_bin;
+    const int grp = tid / Q, seg = tid % Q, ngrp = T / Q;
+    __syncthreads();
+
+    for (int k0 = 0; k0 < K; k0 += bin_chunk) {
+        const int kc = min(bin_chunk, K - k0);
+        // ---- forward: the bins k0 .. k0 + kc - 1, Q lanes per bin, each over the columns seg, seg + Q, ...
+        for (int b0 = 0; b0 < kc; b0 += ngrp) {
+            const int b = b0 + grp;
+            const bool live = b < kc;                    // uniform over a lane group; the shuffles below run for every lane
+            int sm = bd.x + k0 + (live ? b : 0);
+            sm = sm < 0 ? sm + w : sm;
+            int j = (int)(((long long)sm * seg) % w);
+            const int step = (int)(((long long)sm * Q) % w);
+            double gr = 0.0, gi = 0.0;
+            if (live) {
+                for (int x = seg; x < w; x += Q) {
+                    const double2 t = tw[j];
+                    const double g = (double)gray[x];
+                    gr = fma(g, t.x, gr);
+                    gi = fma(g, t.y, gi);
+                    j += step;
+                    j -= j >= w ? w : 0;
+                }
+            }
+            for (int o = Q >> 1; o > 0; o >>= 1) {
+                gr += __shfl_xor(gr, o);
+                gi += __shfl_xor(gi, o);
+            }
+            if (live && seg == 0) bins[b] = make_double2(gr, -gi);      // e^{-i theta}: the imaginary part changes sign
+        }
+        __syncthreads();
+        // ---- backward: every column adds the kc bins; from one bin to the next (s x) mod w moves by x
+#pragma unroll 2
+        for (int b = 0; b < kc; ++b) {
+            const double2 G = bins[b];
+#pragma unroll
+            for (int c = 0; c < CPT; ++c) {
+                const double2 t = tw[js[c]];
+                ar[c] = fma(G.x, t.x, ar[c]);
+                ar[c] = fma(-G.y, t.y, ar[c]);
+                ai[c] = fma(G.x, t.y, ai[c]);
+                ai[c] = fma(G.y, t.x, ai[c]);
+                js[c] += xs[c];
+                js[c] -= js[c] >= w ? w : 0;
+            }
+        }
+        __syncthreads();
+    }
+
+    // ---- angle(ghat)
+#pragma unroll
+    for (int c = 0; c < CPT; ++c) {
+        const int x = tid + c * T;
+        if (x < w) orow[x] = atan2(ai[c], ar[c]);
+    }
+}
+
 }  // namespace ssamd

@@ -63,6 +63,15 @@ inline FtpGeom ftp_geometry(int w)
     return g;
 }
 
+// The one-image kernel (ftp_carrier_kernel): the same columns per thread and threads; twiddles 16 w, a chunk of bins of 16 bytes
+// each, gray bytes w -- 138 KiB at FTP_MAX_W.
+inline FtpGeom ftp_carrier_geometry(int w)
+{
+    FtpGeom g = ftp_geometry(w);
+    g.lds_bytes = 16 * w + 16 * FTP_BIN_CHUNK + ((w + 15) & ~15);
+    return g;
+}
+
 // lanes of a wave that share one bin in the forward pass (a power of two, 4 .. 64): as few as still give every bin of a
 // chunk a lane group in one round, so short bands keep all lanes busy and long ones need few reduction steps
 inline int ftp_lanes_per_bin(int threads, int max_bins)

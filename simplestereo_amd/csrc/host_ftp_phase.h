@@ -35,8 +35,9 @@ int ftp_twiddles(Ctx &c, int w, hipStream_t s, const double2 **tw)
     return SSAMD_OK;
 }
 
-int ftp_launch(Ctx &c, const uint8_t *d_obj, int ch_obj, const uint8_t *d_ref, int ch_ref, int h, int w, const double *fmin,
-               const double *fmax, int unwrap, double tau, double *d_out, hipStream_t s)
+// The kept bins of every row, planned on the host and uploaded to c.ftpBand on `s`, and the twiddle table of the width: what
+// ftp_launch and ftp_carrier_launch (host_ftp_mapping.h) do before their kernel.  max_bins: the longest band.
+int ftp_stage_bands(Ctx &c, int h, int w, const double *fmin, const double *fmax, hipStream_t s, int &max_bins, const double2 **tw)
 {
     int rc;
     // the bands go through pinned staging that the previous call's upload may still be reading
@@ -48,7 +49,7 @@ int ftp_launch(Ctx &c, const uint8_t *d_obj, int ch_obj, const uint8_t *d_ref, i
         HIP_TRY(hipHostMalloc((void **)&c.ftpBandHost, want * 2 * sizeof(int32_t), hipHostMallocDefault));
         c.ftpBandHostCap = want;
     }
-    int max_bins = 0;
+    max_bins = 0;
     for (int y = 0; y < h; ++y) {
         int32_t lo, hi;
         ftp_band_row(w, fmin[y], fmax[y], lo, hi);
@@ -59,8 +60,28 @@ int ftp_launch(Ctx &c, const uint8_t *d_obj, int ch_obj, const uint8_t *d_ref, i
     if ((rc = c.ftpBand.reserve((size_t)h * 2 * sizeof(int32_t)))) return rc;
     HIP_TRY(hipMemcpyAsync(c.ftpBand.ptr, c.ftpBandHost, (size_t)h * 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
     HIP_TRY(hipEventRecord(c.ftp_band_copied, s));
+    return ftp_twiddles(c, w, s, tw);
+}
+
+// the unwrapping that follows a wrapped map on the same stream: 0 none, 1 IIR (d_phase, a buffer of the context's, -> d_out),
+// 2 np.unwrap along x then y (in place in d_out)
+int ftp_unwrap_tail(Ctx &c, int unwrap, double tau, const double *d_phase, int h, int w, double *d_out, hipStream_t s)
+{
+    if (unwrap == 2) {
+        NpuXY q;
+        int rc = npu_xy_check(1, h, w, q);               // cannot fail: ftp_check has asked before anything was enqueued
+        if (rc) return rc;
+        return npu_xy_launch(c, q, d_out, h, w, d_out, s);
+    }
+    return unwrap ? unwrap_launch(c, d_phase, 1, h, w, tau, d_out, s) : SSAMD_OK;
+}
+
+int ftp_launch(Ctx &c, const uint8_t *d_obj, int ch_obj, const uint8_t *d_ref, int ch_ref, int h, int w, const double *fmin,
+               const double *fmax, int unwrap, double tau, double *d_out, hipStream_t s)
+{
+    int rc, max_bins;
     const double2 *tw = nullptr;
-    if ((rc = ftp_twiddles(c, w, s, &tw))) return rc;
+    if ((rc = ftp_stage_bands(c, h, w, fmin, fmax, s, max_bins, &tw))) return rc;
     double *d_phase = d_out;
     if (unwrap == 1) {                                   // the wavefront kernel does not work in place
         if ((rc = c.ftpPhase.reserve((size_t)h * w * sizeof(double)))) return rc;
@@ -79,12 +100,7 @@ int ftp_launch(Ctx &c, const uint8_t *d_obj, int ch_obj, const uint8_t *d_ref, i
     };
     static constexpr decltype(&ftp_phase_kernel<1>) kernels[4] = {ftp_phase_kernel<1>, ftp_phase_kernel<2>, ftp_phase_kernel<4>, ftp_phase_kernel<8>};
     if ((rc = launch(kernels[g.cpt == 1 ? 0 : g.cpt == 2 ? 1 : g.cpt == 4 ? 2 : 3]))) return rc;      // by columns per thread
-    if (unwrap == 2) {
-        NpuXY q;
-        if ((rc = npu_xy_check(1, h, w, q))) return rc;  // cannot fail: ftp_check has asked before anything was enqueued
-        return npu_xy_launch(c, q, d_out, h, w, d_out, s);
-    }
-    return unwrap ? unwrap_launch(c, d_phase, 1, h, w, tau, d_out, s) : SSAMD_OK;
+    return ftp_unwrap_tail(c, unwrap, tau, d_phase, h, w, d_out, s);
 }
 }  // namespace
 
