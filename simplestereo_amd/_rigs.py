@@ -237,7 +237,8 @@ def _remap(img, mapx, mapy, interpolation=INTER_LINEAR):
 
 def _cross_matrix(v):
     v = np.asarray(v, dtype=np.float64).ravel()
-    return np.array([[0, -v[2], v[1]], [v[2], 0, -v[0]], [-v[1], v[0], 0]])
+    # float32, as the reference's utils.getCrossProductMatrix (utils.py:229-232) builds it: F carries that rounding
+    return np.array([[0, -v[2], v[1]], [v[2], 0, -v[0]], [-v[1], v[0], 0]], dtype=np.float32)
 
 
 def _corners_after(H, K, dims, distCoeffs):
@@ -381,14 +382,17 @@ class StereoRig:
         return np.linalg.norm(self.getCenters()[1])
 
     def getFundamentalMatrix(self):
-        """F (computed from the camera parameters when not set; Hartley & Zisserman form)."""
+        """F (computed from the camera parameters when not set; Hartley & Zisserman form).  The cross-product matrix of
+        ``K1 R^T T`` is rounded to float32 before the float64 products, as the reference's
+        ``utils.getCrossProductMatrix`` does: F is the reference's bit for bit, 1e-7 relative from the all-float64 value."""
         if self.F is None:
             vv = _cross_matrix(self.intrinsic1.dot(self.R.T).dot(self.T))
             self.F = (np.linalg.inv(self.intrinsic2).T).dot(self.R).dot(self.intrinsic1.T).dot(vv)
         return self.F
 
     def getEssentialMatrix(self):
-        """E = K2^T F K1 when not set."""
+        """E = K2^T F K1 when not set.  Computed from :meth:`getFundamentalMatrix`, E inherits its float32 rounding of the
+        cross-product matrix, as in the reference."""
         if self.E is None:
             self.E = self.intrinsic2.T.dot(self.getFundamentalMatrix()).dot(self.intrinsic1)
         return self.E

@@ -181,17 +181,18 @@ def geometry(rig):
     return g
 
 
-def cloud_dense(g, decoded, x0, y0):
-    """float64 [h, w, 3]: the point of every valid pixel of `decoded` [h, w, 2] (region origin x0, y0), NaN at the invalid ones.
+def cloud_dense(g, decoded, x0, y0, dtype=np.float64):
+    """`dtype` [h, w, 3]: the point of every valid pixel of `decoded` [h, w, 2] (region origin x0, y0), NaN at the invalid ones.
     pc = (x + 0.5, y + 0.5), pp = (xDec + 0.5, yDec + 0.5) (active.py:1236-1237), then the lines of
-    _ftp_cloud_ref.cloud_from_geometry from undistort_points to the end, with (Xh, Yh) = pp."""
-    g = np.asarray(g, dtype=np.float64)
+    _ftp_cloud_ref.cloud_from_geometry from undistort_points to the end, with (Xh, Yh) = pp.  np.float64 is the restatement;
+    np.longdouble evaluates the same function of the fp64 geometry as a truth."""
+    g = np.asarray(g, dtype=np.float64).astype(dtype)
     h, w = decoded.shape[:2]
     yy, xx = np.mgrid[0:h, 0:w]
-    u = (xx + x0).astype(np.float64) + 0.5
-    v = (yy + y0).astype(np.float64) + 0.5
-    Xh = decoded[..., 0].astype(np.float64) + 0.5
-    Yh = decoded[..., 1].astype(np.float64) + 0.5
+    u = (xx + x0).astype(dtype) + dtype(0.5)
+    v = (yy + y0).astype(dtype) + dtype(0.5)
+    Xh = decoded[..., 0].astype(dtype) + dtype(0.5)
+    Yh = decoded[..., 1].astype(dtype) + dtype(0.5)
     with np.errstate(all="ignore"):
         hx, hy = C.undistort_points(g, Xh, Yh)
         R1, R2, Ri, baseline = g[40:49], g[49:58], g[58:67], g[67]

@@ -208,7 +208,7 @@ class Rig:
         self.period, self.fp = period, 1 / period
         self.peak = central_peak(fringe_width, period, shift)
         v = self.K1.dot(self.R.T).dot(self.T).ravel()
-        vv = np.array([[0, -v[2], v[1]], [v[2], 0, -v[0]], [-v[1], v[0], 0]])
+        vv = np.array([[0, -v[2], v[1]], [v[2], 0, -v[0]], [-v[1], v[0], 0]], dtype=np.float32)       # utils.py:229-232: float32
         self.F = (np.linalg.inv(self.K2).T).dot(self.R).dot(self.K1.T).dot(vv)
         Po2 = self.K2.dot(np.hstack((self.R, self.T)))
         B = -np.linalg.inv(Po2[:, :3]).dot(Po2[:, 3])
@@ -303,9 +303,10 @@ def render(rig, period, fringe_dims=(1280, 720), z0=1000.0, bump=8.0, amplitude=
 
 
 # ------------------------------------------------------------------------------------------------ the pipeline
-def pipeline(rig, fringe, period, frame, roi=None, radius_factor=0.5, phase_of=None):
+def pipeline(rig, fringe, period, frame, roi=None, radius_factor=0.5, phase_of=None, unwrap=None):
     """StereoFTP(rig, fringe, period).getCloud(frame, radius_factor, roi) in numpy (active.py:631-841) -> dict of every stage.
-    `phase_of(obj, ref, fc, radius_factor)` replaces the np.fft demodulation (e.g. the np.longdouble phase of _ftp_ref)."""
+    `phase_of(obj, ref, fc, radius_factor)` replaces the np.fft demodulation (e.g. the np.longdouble phase of _ftp_ref);
+    `unwrap(wrapped)` is the reference's `unwrappingMethod`."""
     rg = Rig(rig, period, fringe.shape[1])
     gray = np.max(fringe, axis=2)
     W, H = rg.res1
@@ -322,10 +323,10 @@ def pipeline(rig, fringe, period, frame, roi=None, radius_factor=0.5, phase_of=N
     ref = reference_image(gray, g, x0, y0, w, h)
     fmin, fmax = P.band(fc, radius_factor, h)
     wrapped = (phase_of or P.ftp_phase_numpy)(cut, ref, fc, radius_factor)
-    phase = np.unwrap(np.unwrap(wrapped, discont=np.pi, axis=1), discont=np.pi, axis=0)
+    phase = np.unwrap(np.unwrap(wrapped, discont=np.pi, axis=1), discont=np.pi, axis=0) if unwrap is None else unwrap(wrapped)
     k = C.fringe_order(g, fp, phase, idx, rg.peak, x0, y0)
     cloud = C.cloud_from_geometry(g, phase, k, x0, y0)
-    return {"undistorted": cut, "stripe": stripe, "stripe_indexes": idx, "z_plane": z_plane, "fc": fc, "geom": g, "ref": ref,
+    return {"undistorted": cut, "stripe": stripe, "stripe_indexes": idx, "world": world, "z_plane": z_plane, "fc": fc, "geom": g, "ref": ref,
             "fmin": fmin, "fmax": fmax, "wrapped": wrapped, "phase": phase, "k": k, "cloud": cloud}
 
 
