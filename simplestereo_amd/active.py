@@ -381,6 +381,41 @@ def _low_level_rectify(rig):
     return rect1, rect2, rot
 
 
+def _r_inv4(common):
+    """The reference's 4 x 4 ``R_inv`` (``active.py:398-401``): the inverse of the common orientation, padded"""
+    R_inv = np.eye(4)
+    R_inv[:3, :3] = np.linalg.inv(common)
+    return R_inv
+
+
+def _triangulation_geom(rig, dist, rect1, rect2, common_inv):
+    """``geom`` with what the triangulation reads (``[12:37]`` and ``[40:68]``: K2, ``distCoeffs2``, the rectifying transforms, the
+    inverse common orientation, the baseline) and 0 elsewhere: the part all three geometry builders share"""
+    K2 = np.asarray(rig.intrinsic2, dtype=np.float64)
+    g = np.zeros(NGEOM)
+    g[12:16] = K2[0, 0], K2[1, 1], K2[0, 2], K2[1, 2]
+    g[16:28] = dist[:12]
+    g[28:37] = K2.ravel()
+    g[40:49] = rect1.ravel()
+    g[49:58] = rect2.ravel()
+    g[58:67] = common_inv.ravel()
+    g[67] = rig.getBaseline()
+    return g
+
+
+def _cached_maps(cache, rig, device=None):
+    """The float32 (mapx, mapy) of ``cv2.undistort`` of a rig's camera, on the host (``device`` None) or as tensors on a device,
+    built on first use and kept in ``cache``, the dict ``StereoFTP`` and ``GrayCode`` hold per instance."""
+    if "host" not in cache:
+        cache["host"] = _undistort_maps(rig)
+    if device is None:
+        return cache["host"]
+    if "maps " + str(device) not in cache:
+        import torch
+        cache["maps " + str(device)] = tuple(torch.from_numpy(m).to(device) for m in cache["host"])
+    return cache["maps " + str(device)]
+
+
 class FtpGeometry:
     """What ``ftpCloud`` and ``ftpFringeOrder`` read from a rig, a reference plane and a fringe period: ``geom``, the
     ``SSAMD_FTP_CLOUD_NGEOM`` doubles of ``ssamd_ftp_cloud`` (layout in ``include/ssamd.h``), and ``roi = (x, y, w, h)``."""
@@ -434,13 +469,14 @@ def ftpGeometry(rig, z_plane, period, roi=None):
     ep = ep / ep[2]
     fp = 1 / per
     rect1, rect2, common = _low_level_rectify(rig)
-    g = np.concatenate([M.ravel(), T, [K2[0, 0], K2[1, 1], K2[0, 2], K2[1, 2]], dist[:12], K2.ravel(), ep[:2],
-                        [2 * np.pi * fp], rect1.ravel(), rect2.ravel(), np.linalg.inv(common).ravel(),
-                        [rig.getBaseline()]]).astype(np.float64)
-    assert g.shape == (NGEOM,)
+    g = _triangulation_geom(rig, dist, rect1, rect2, np.linalg.inv(common))
+    g[0:9] = M.ravel()
+    g[9:12] = T
+    g[37:39] = ep[:2]
+    g[39] = 2 * np.pi * fp
     if not np.isfinite(g).all():
         raise ValueError("the rig, z_plane and period give a geometry that is not finite")
-    return FtpGeometry(np.ascontiguousarray(g), box, fp)
+    return FtpGeometry(g, box, fp)
 
 
 def _geometry(rig, z_plane, period, roi):
@@ -451,8 +487,8 @@ def _geometry(rig, z_plane, period, roi):
     return ftpGeometry(rig, z_plane, period, roi)
 
 
-def _phase_map(phase, box):
-    """-> (contiguous map, is it on a device), checked against the roi"""
+def _phase_dims(phase):
+    """(H, W) of a float64 [H, W] array or device tensor"""
     dev = _is_device_tensor(phase)
     if not (dev or isinstance(phase, np.ndarray)):
         raise TypeError("phaseUnwrapped must be a float64 ndarray or a CUDA/HIP torch.float64 tensor")
@@ -464,10 +500,25 @@ def _phase_map(phase, box):
         raise TypeError("phaseUnwrapped must be a float64 array")
     if phase.ndim != 2:
         raise ValueError("phaseUnwrapped must be [H, W]")
-    if (int(phase.shape[1]), int(phase.shape[0])) != (box[2], box[3]):
-        raise ValueError("phaseUnwrapped is %d x %d but the roi is %d x %d (width x height)" %
-                         (phase.shape[1], phase.shape[0], box[2], box[3]))
-    return phase, dev
+    return int(phase.shape[0]), int(phase.shape[1])
+
+
+def _phase_map(phase, box):
+    """-> (map, is it on a device), checked against the roi"""
+    h, w = _phase_dims(phase)
+    if (w, h) != (box[2], box[3]):
+        raise ValueError("phaseUnwrapped is %d x %d but the roi is %d x %d (width x height)" % (w, h, box[2], box[3]))
+    return phase, _is_device_tensor(phase)
+
+
+def _cloud_phase(phase, box):
+    """The checked map as the cloud kernels read it: a tensor contiguous and, for their 16-byte loads of two phases, aligned"""
+    phase, dev = _phase_map(phase, box)
+    if dev:
+        phase = phase.contiguous()
+        if phase.data_ptr() % 16:
+            phase = phase.clone()     # a view at an odd storage offset
+    return phase
 
 
 def _project_x(g, u, v):
@@ -573,12 +624,8 @@ def ftpCloud(phaseUnwrapped, rig, z_plane=None, period=None, k=0, roi=None):
     """
     G = _geometry(rig, z_plane, period, roi)
     order = _finite(k, "k")
-    phase, dev = _phase_map(phaseUnwrapped, G.roi)
+    phase = _cloud_phase(phaseUnwrapped, G.roi)
     x0, y0, w, h = G.roi
-    if dev:
-        phase = phase.contiguous()
-        if phase.data_ptr() % 16:
-            phase = phase.clone()     # a view at an odd storage offset: the kernel reads two phases per 16-byte load
     return _native.run("ssamd_ftp_cloud", (phase,), (h, w, 3), lambda src, out: (src, h, w, x0, y0, G.geom.ctypes.data, order, out), _INVALID)
 
 
@@ -818,12 +865,8 @@ class StereoFTP:
         self.Rectify1, self.Rectify2, commonR = _low_level_rectify(stereoRig)
         ep = self.stereoRig.intrinsic2.dot(self.stereoRig.T)
         self.ep = ep / ep[2]
-        R_inv = np.linalg.inv(commonR)
-        R_inv = np.hstack((np.vstack((R_inv, np.zeros((1, 3)))), np.zeros((4, 1))))
-        R_inv[3, 3] = 1
-        self.R_inv = R_inv
-        self._undistort_maps = None      # float32 (mapx, mapy) of cv2.undistort, host
-        self._on_device = {}             # device -> (gray fringe, mapx, mapy) tensors
+        self.R_inv = _r_inv4(commonR)
+        self._cache = {}                 # _cached_maps' entries, and per device (gray fringe, mapx, mapy) tensors
 
     @staticmethod
     def convertGrayscale(img):
@@ -831,17 +874,14 @@ class StereoFTP:
         return np.max(img, axis=2)
 
     def _device_state(self, device):
-        import torch
-        if str(device) not in self._on_device:
-            mx, my = self._host_maps()
-            self._on_device[str(device)] = (torch.from_numpy(np.ascontiguousarray(self.fringe)).to(device),
-                                            torch.from_numpy(mx).to(device), torch.from_numpy(my).to(device))
-        return self._on_device[str(device)]
+        if str(device) not in self._cache:
+            import torch
+            self._cache[str(device)] = ((torch.from_numpy(np.ascontiguousarray(self.fringe)).to(device),)
+                                        + _cached_maps(self._cache, self.stereoRig, device))
+        return self._cache[str(device)]
 
     def _host_maps(self):
-        if self._undistort_maps is None:
-            self._undistort_maps = _undistort_maps(self.stereoRig)
-        return self._undistort_maps
+        return _cached_maps(self._cache, self.stereoRig)
 
     def _undistort(self, img):
         """``cv2.undistort(img, K1, distCoeffs1)``: the float32 maps of ``initUndistortRectifyMap(K1, D1, I, K1, res1)`` and a
@@ -1026,22 +1066,6 @@ def ftpStripePhase(phaseUnwrapped, stripe):
     return float(np.mean(np.where(inside, val, 0.0)))
 
 
-def _phase_dims(phase):
-    """(H, W) of a float64 [H, W] array or device tensor"""
-    dev = _is_device_tensor(phase)
-    if not (dev or isinstance(phase, np.ndarray)):
-        raise TypeError("phaseUnwrapped must be a float64 ndarray or a CUDA/HIP torch.float64 tensor")
-    if dev:
-        import torch
-        if phase.dtype != torch.float64:
-            raise TypeError("phaseUnwrapped must be a float64 tensor")
-    elif phase.dtype != np.float64:
-        raise TypeError("phaseUnwrapped must be a float64 array")
-    if phase.ndim != 2:
-        raise ValueError("phaseUnwrapped must be [H, W]")
-    return int(phase.shape[0]), int(phase.shape[1])
-
-
 class FtpMappingGeometry(FtpGeometry):
     """What ``ftpMappingCloud`` reads from a rig and a fringe period: ``geom`` (the ``SSAMD_FTP_CLOUD_NGEOM`` doubles with
     only the triangulation's entries and ``2 pi fp`` filled in), ``F`` (float64 [9], the fundamental matrix row by row) and
@@ -1071,18 +1095,10 @@ def ftpMappingGeometry(rig, period, roi=None):
         raise ValueError("period must not be 0")
     box = _roi(roi, rig.res1)
     dist = _dist_vector(rig.distCoeffs2)                      # NotImplementedError for a tilted sensor
-    K2 = np.asarray(rig.intrinsic2, dtype=np.float64)
     rect1, rect2, common = _low_level_rectify(rig)
     fp = 1 / per
-    g = np.zeros(NGEOM)
-    g[12:16] = K2[0, 0], K2[1, 1], K2[0, 2], K2[1, 2]
-    g[16:28] = dist[:12]
-    g[28:37] = K2.ravel()
+    g = _triangulation_geom(rig, dist, rect1, rect2, np.linalg.inv(common))
     g[39] = 2 * np.pi * fp
-    g[40:49] = rect1.ravel()
-    g[49:58] = rect2.ravel()
-    g[58:67] = np.linalg.inv(common).ravel()
-    g[67] = rig.getBaseline()
     F = np.ascontiguousarray(np.asarray(rig.getFundamentalMatrix(), dtype=np.float64).reshape(9))
     if not (np.isfinite(g).all() and np.isfinite(F).all()):
         raise ValueError("the rig and period give a geometry that is not finite")
@@ -1133,12 +1149,8 @@ def ftpMappingCloud(phaseUnwrapped, rig, period=None, stripeCentralPeak=None, th
         G = ftpMappingGeometry(rig, period, roi)
     peak = _finite(stripeCentralPeak, "stripeCentralPeak")
     theta = _finite(theta_shift, "theta_shift")
-    phase, dev = _phase_map(phaseUnwrapped, G.roi)
+    phase = _cloud_phase(phaseUnwrapped, G.roi)
     x0, y0, w, h = G.roi
-    if dev:
-        phase = phase.contiguous()
-        if phase.data_ptr() % 16:
-            phase = phase.clone()     # a view at an odd storage offset: the kernel reads two phases per 16-byte load
     gp, Fp = (a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) for a in (G.geom, G.F))
     return _native.run("ssamd_ftp_mapping_cloud", (phase,), (h, w, 3), lambda src, out: (src, h, w, x0, y0, gp, Fp, theta, peak, out), _INVALID)
 
@@ -1503,22 +1515,11 @@ class GrayCode:
         self._proj = _proj_res(rig.res2)
         self.num_patterns = 2 * (self._proj[2] + self._proj[3])
         self.Rectify1, self.Rectify2, commonR = _low_level_rectify(rig)
-        R_inv = np.linalg.inv(commonR)
-        R_inv = np.hstack((np.vstack((R_inv, np.zeros((1, 3)))), np.zeros((4, 1))))
-        R_inv[3, 3] = 1
-        self.R_inv = R_inv
-        self._undistort_maps = None      # float32 (mapx, mapy) of cv2.undistort, host
-        self._on_device = {}             # device -> (mapx, mapy) tensors
+        self.R_inv = _r_inv4(commonR)
+        self._cache = {}                 # _cached_maps' entries
 
     def _maps(self, device=None):
-        if self._undistort_maps is None:
-            self._undistort_maps = _undistort_maps(self.rig)
-        if device is None:
-            return self._undistort_maps
-        if str(device) not in self._on_device:
-            import torch
-            self._on_device[str(device)] = tuple(torch.from_numpy(m).to(device) for m in self._undistort_maps)
-        return self._on_device[str(device)]
+        return _cached_maps(self._cache, self.rig, device)
 
     def _geometry(self):
         """The ``SSAMD_FTP_CLOUD_NGEOM`` doubles of ``ssamd_graycode_cloud``: only what the triangulation reads -- K2,
@@ -1526,15 +1527,7 @@ class GrayCode:
         phase period is in it, so ``T[2] == 0`` is fine."""
         rig = self.rig
         dist = _dist_vector(rig.distCoeffs2)                      # NotImplementedError for a tilted sensor; None is no distortion
-        K2 = np.asarray(rig.intrinsic2, dtype=np.float64)
-        g = np.zeros(NGEOM)
-        g[12:16] = K2[0, 0], K2[1, 1], K2[0, 2], K2[1, 2]
-        g[16:28] = dist[:12]
-        g[28:37] = K2.ravel()
-        g[40:49] = self.Rectify1.ravel()
-        g[49:58] = self.Rectify2.ravel()
-        g[58:67] = self.R_inv[:3, :3].ravel()
-        g[67] = rig.getBaseline()
+        g = _triangulation_geom(rig, dist, self.Rectify1, self.Rectify2, self.R_inv[:3, :3])
         if not np.isfinite(g).all():
             raise ValueError("the rig gives a geometry that is not finite")
         return g

@@ -1,7 +1,8 @@
 // FTP phase -> point cloud: the triangulation of the reference's StereoFTP.getCloud (active.py:776-841, with the projector
 // coordinates of _getProjectorMapping, :463-485), which is 2 W H cv2.projectPoints, W H cv2.undistortPoints and three
 // cv2.perspectiveTransform there.  One pointwise fp64 kernel: 8 B of phase in, 24 B of point out, nothing else read from
-// memory -- the geometry arrives by value (FtpCloudGeom, as Mat4 in rig_kernels.hip.h).
+// memory -- the geometry arrives by value (FtpCloudGeom, as Mat4 in rig_kernels.hip.h).  The kernel is ftp_cloud_pixel in
+// ftp_cloud_frame; ftp_mapping_cloud_kernel (ftp_mapping_kernels.hip.h) is another pixel function in the same frame.
 //
 // Arithmetic contract: every pixel is evaluated by the operations of tests/_ftp_cloud_ref.py (cloud_from_geometry) in that
 // order, each rounded once: no contraction into fused multiply-adds, IEEE divisions.  With the same geometry
@@ -121,15 +122,15 @@ __device__ __forceinline__ void ftp_cloud_pixel(const FtpCloudGeom &G, double u,
     ftp_triangulate<MODEL>(G, u, v, Xh, Yh, o);
 }
 
-// phase [h][w] (ROI origin x0, y0 in the camera image) -> out [h][w][3].  Pixels are one flattened index (npix = h w < 2^31):
-// rows are not a grid dimension, so h is not limited by one.  A thread owns the two pixels 2q, 2q + 1 (one 16-byte phase
-// read); whole waves iterate, so that a wave's up to 128 x 24 bytes go out as three contiguous 1 KiB stores: the 16-byte
-// chunks are transposed through LDS and lane l writes chunks l, l + 64, l + 128 (reproject_kernel's pattern).  phase and out
-// must be 16-byte aligned.
-template <int MODEL>
-__global__ __launch_bounds__(FTP_CLOUD_THREADS) void ftp_cloud_kernel(const double *__restrict__ phase, double *__restrict__ out,
-                                                                      long long npix, int w, int x0, int y0, double kshift,
-                                                                      const FtpCloudGeom G)
+// The frame of the pointwise cloud kernels (ftp_cloud_kernel here, ftp_mapping_cloud_kernel of ftp_mapping_kernels.hip.h):
+// phase [h][w] (ROI origin x0, y0 in the camera image) -> out [h][w][3], with pixel(u, v, phase, o) the per-pixel step from a pixel
+// centre and its phase to the point o[0..2].  Pixels are one flattened index (npix = h w < 2^31): rows are not a grid dimension,
+// so h is not limited by one.  A thread owns the two pixels 2q, 2q + 1 (one 16-byte phase read); whole waves iterate, so that a
+// wave's up to 128 x 24 bytes go out as three contiguous 1 KiB stores: the 16-byte chunks are transposed through LDS and lane l
+// writes chunks l, l + 64, l + 128 (reproject_kernel's pattern).  phase and out must be 16-byte aligned; blockDim.x is
+// FTP_CLOUD_THREADS.  (The kernels' own parameters are __restrict__; the frame's need not be.)
+template <class Pixel>
+__device__ __forceinline__ void ftp_cloud_frame(const double *phase, double *out, long long npix, int w, int x0, int y0, Pixel pixel)
 {
 #pragma clang fp contract(off)
     __shared__ double2 xchg[FTP_CLOUD_WAVES][192];
@@ -150,9 +151,10 @@ __global__ __launch_bounds__(FTP_CLOUD_THREADS) void ftp_cloud_kernel(const doub
             const unsigned int yy = (unsigned int)p / (unsigned int)w, xx = (unsigned int)p - yy * (unsigned int)w;
             const bool wrap = xx + 1 == (unsigned int)w;          // the second pixel starts the next row
             double o[6];
-            ftp_cloud_pixel<MODEL>(G, ((double)xx + (double)x0) + 0.5, ((double)yy + (double)y0) + 0.5, ph0 + kshift, o);
-            ftp_cloud_pixel<MODEL>(G, ((double)(wrap ? 0u : xx + 1) + (double)x0) + 0.5, ((double)(wrap ? yy + 1 : yy) + (double)y0) + 0.5,
-                                   ph1 + kshift, o + 3);
+            // the pixel centre, (x + x0) + 0.5: the restatement of the mapping spells it (x + 0.5) + x0, and both sums are exact in
+            // fp64 (integers below 2^32, then one half), so the one spelling gives either restatement's value
+            pixel(((double)xx + (double)x0) + 0.5, ((double)yy + (double)y0) + 0.5, ph0, o);
+            pixel(((double)(wrap ? 0u : xx + 1) + (double)x0) + 0.5, ((double)(wrap ? yy + 1 : yy) + (double)y0) + 0.5, ph1, o + 3);
             double2 *const mine = xchg[wave] + 3 * lane;
             mine[0] = make_double2(o[0], o[1]);
             mine[1] = make_double2(o[2], o[3]);
@@ -172,6 +174,18 @@ __global__ __launch_bounds__(FTP_CLOUD_THREADS) void ftp_cloud_kernel(const doub
         asm volatile("" ::: "memory");
         __builtin_amdgcn_wave_barrier();
     }
+}
+
+// The frame with ftp_cloud_pixel on the phase shifted by the fringe order (kshift = 2 pi k).
+template <int MODEL>
+__global__ __launch_bounds__(FTP_CLOUD_THREADS) void ftp_cloud_kernel(const double *__restrict__ phase, double *__restrict__ out,
+                                                                      long long npix, int w, int x0, int y0, double kshift,
+                                                                      const FtpCloudGeom G)
+{
+    ftp_cloud_frame(phase, out, npix, w, x0, y0, [&](double u, double v, double ph, double *o) {
+#pragma clang fp contract(off)
+        ftp_cloud_pixel<MODEL>(G, u, v, ph + kshift, o);
+    });
 }
 
 }  // namespace ssamd

@@ -46,29 +46,22 @@ inline void ftp_band_row(int w, double fmin, double fmax, int32_t &slo, int32_t 
     if (slo > shi) { slo = 0; shi = -1; }       // one spelling of "empty"
 }
 
-// Launch shape for rows of w columns: CPT output columns per thread (the kernel's template argument), threads per workgroup
-// (whole waves, at most FTP_THREADS_MAX), dynamic LDS bytes.
+// Launch shape for rows of w columns of `images` images (2: ftp_phase_kernel, 1: ftp_carrier_kernel): CPT output columns per
+// thread (the kernel's template argument), threads per workgroup (whole waves, at most FTP_THREADS_MAX), dynamic LDS bytes.
 struct FtpGeom { int cpt, threads, lds_bytes; };
 
 constexpr int FTP_MAX_W = 8192;                 // twiddles 16 w + gray pairs 2 w + a chunk of bins: 148 KiB of the 160 KiB
 constexpr int FTP_THREADS_MAX = 1024;
-constexpr int FTP_BIN_CHUNK = 128;              // bins held in LDS at a time (32 bytes each)
+constexpr int FTP_BIN_CHUNK = 128;              // bins held in LDS at a time (16 bytes each and image)
 
-inline FtpGeom ftp_geometry(int w)
+// LDS of ftp_dft_row: twiddles 16 w, a chunk of bins of 16 bytes per image, gray bytes w per image (148 KiB with two images at
+// FTP_MAX_W, 138 KiB with one)
+inline FtpGeom ftp_geometry(int w, int images)
 {
     FtpGeom g;
     g.cpt = w <= 1024 ? 1 : w <= 2048 ? 2 : w <= 4096 ? 4 : 8;
     g.threads = (((w + g.cpt - 1) / g.cpt) + 63) / 64 * 64;
-    g.lds_bytes = 16 * w + 32 * FTP_BIN_CHUNK + ((2 * w + 15) & ~15);
-    return g;
-}
-
-// The one-image kernel (ftp_carrier_kernel): the same columns per thread and threads; twiddles 16 w, a chunk of bins of 16 bytes
-// each, gray bytes w -- 138 KiB at FTP_MAX_W.
-inline FtpGeom ftp_carrier_geometry(int w)
-{
-    FtpGeom g = ftp_geometry(w);
-    g.lds_bytes = 16 * w + 16 * FTP_BIN_CHUNK + ((w + 15) & ~15);
+    g.lds_bytes = 16 * w + 16 * images * FTP_BIN_CHUNK + ((images * w + 15) & ~15);
     return g;
 }
 

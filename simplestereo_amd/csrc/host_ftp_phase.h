@@ -1,4 +1,5 @@
-// Host section of ssamd_api.hip: FTP phase (ftp_kernels.hip.h, ftp_plan.h) -- check, twiddle tables, launch, entry points.
+// Host section of ssamd_api.hip: FTP phase of an image pair and of one image (ftp_kernels.hip.h, ftp_plan.h) -- check, twiddle
+// tables, the one launch, entry points (include/ssamd.h; the one-image pair in include/ssamd_ftp_mapping.h).
 namespace {
 // band planning, table and launches of ssamd_ftp_phase*; the caller holds the context and has ordered the scratch (ScratchOrder)
 static_assert(FTP_MAX_W == SSAMD_FTP_MAX_W, "ssamd.h states the width limit of ftp_plan.h");
@@ -36,7 +37,7 @@ int ftp_twiddles(Ctx &c, int w, hipStream_t s, const double2 **tw)
 }
 
 // The kept bins of every row, planned on the host and uploaded to c.ftpBand on `s`, and the twiddle table of the width: what
-// ftp_launch and ftp_carrier_launch (host_ftp_mapping.h) do before their kernel.  max_bins: the longest band.
+// ftp_dft_launch does before its kernel.  max_bins: the longest band.
 int ftp_stage_bands(Ctx &c, int h, int w, const double *fmin, const double *fmax, hipStream_t s, int &max_bins, const double2 **tw)
 {
     int rc;
@@ -76,8 +77,10 @@ int ftp_unwrap_tail(Ctx &c, int unwrap, double tau, const double *d_phase, int h
     return unwrap ? unwrap_launch(c, d_phase, 1, h, w, tau, d_out, s) : SSAMD_OK;
 }
 
-int ftp_launch(Ctx &c, const uint8_t *d_obj, int ch_obj, const uint8_t *d_ref, int ch_ref, int h, int w, const double *fmin,
-               const double *fmax, int unwrap, double tau, double *d_out, hipStream_t s)
+// One DFT launch and its unwrapping tail.  images == 2: ftp_phase_kernel of d_obj against d_ref; images == 1: ftp_carrier_kernel of
+// d_obj alone (d_ref and ch_ref are not read).
+int ftp_dft_launch(Ctx &c, int images, const uint8_t *d_obj, int ch_obj, const uint8_t *d_ref, int ch_ref, int h, int w, const double *fmin,
+                   const double *fmax, int unwrap, double tau, double *d_out, hipStream_t s)
 {
     int rc, max_bins;
     const double2 *tw = nullptr;
@@ -87,19 +90,22 @@ int ftp_launch(Ctx &c, const uint8_t *d_obj, int ch_obj, const uint8_t *d_ref, i
         if ((rc = c.ftpPhase.reserve((size_t)h * w * sizeof(double)))) return rc;
         d_phase = (double *)c.ftpPhase.ptr;
     }
-    const FtpGeom g = ftp_geometry(w);
+    const FtpGeom g = ftp_geometry(w, images);
     const int q = ftp_lanes_per_bin(g.threads, std::max(max_bins, 1));
-    auto launch = [&](auto kernel) -> int {
+    auto launch = [&](auto kernel, auto... images) -> int {
         int r = grant_dyn_lds(c, reinterpret_cast<const void *>(kernel), g.lds_bytes);
         if (r) return r;
         Timed t(c, s, SSAMD_K_FTP);
-        hipLaunchKernelGGL(kernel, dim3(h), dim3(g.threads), g.lds_bytes, s, d_obj, ch_obj, d_ref, ch_ref, w,
-                           (const int2 *)c.ftpBand.ptr, tw, q, FTP_BIN_CHUNK, d_phase);
+        hipLaunchKernelGGL(kernel, dim3(h), dim3(g.threads), g.lds_bytes, s, images..., w, (const int2 *)c.ftpBand.ptr, tw, q, FTP_BIN_CHUNK,
+                           d_phase);
         HIP_TRY(hipGetLastError());
         return SSAMD_OK;
     };
-    static constexpr decltype(&ftp_phase_kernel<1>) kernels[4] = {ftp_phase_kernel<1>, ftp_phase_kernel<2>, ftp_phase_kernel<4>, ftp_phase_kernel<8>};
-    if ((rc = launch(kernels[g.cpt == 1 ? 0 : g.cpt == 2 ? 1 : g.cpt == 4 ? 2 : 3]))) return rc;      // by columns per thread
+    static constexpr decltype(&ftp_phase_kernel<1>) pair[4] = {ftp_phase_kernel<1>, ftp_phase_kernel<2>, ftp_phase_kernel<4>, ftp_phase_kernel<8>};
+    static constexpr decltype(&ftp_carrier_kernel<1>) one[4] = {ftp_carrier_kernel<1>, ftp_carrier_kernel<2>, ftp_carrier_kernel<4>,
+                                                                ftp_carrier_kernel<8>};
+    const int i = g.cpt == 1 ? 0 : g.cpt == 2 ? 1 : g.cpt == 4 ? 2 : 3;                                  // by columns per thread
+    if ((rc = images == 2 ? launch(pair[i], d_obj, ch_obj, d_ref, ch_ref) : launch(one[i], d_obj, ch_obj))) return rc;
     return ftp_unwrap_tail(c, unwrap, tau, d_phase, h, w, d_out, s);
 }
 }  // namespace
@@ -122,8 +128,8 @@ int ssamd_ftp_phase(const uint8_t *img_obj, int ch_obj, const uint8_t *img_ref, 
     const size_t px = (size_t)h * w;
     return host_route(device, {{&Ctx::imgL, img_obj, px * ch_obj}, {&Ctx::imgR, img_ref, px * ch_ref}}, {&Ctx::uwOut, out, px * sizeof(double)},
                       [&](Ctx &c, hipStream_t s) {
-                          return ftp_launch(c, (const uint8_t *)c.imgL.ptr, ch_obj, (const uint8_t *)c.imgR.ptr, ch_ref, h, w, fmin, fmax, unwrap, tau,
-                                            (double *)c.uwOut.ptr, s);
+                          return ftp_dft_launch(c, 2, (const uint8_t *)c.imgL.ptr, ch_obj, (const uint8_t *)c.imgR.ptr, ch_ref, h, w, fmin, fmax, unwrap,
+                                                tau, (double *)c.uwOut.ptr, s);
                       });
 }
 
@@ -136,6 +142,31 @@ int ssamd_ftp_phase_device(const uint8_t *d_img_obj, int ch_obj, const uint8_t *
     CtxLock c;
     if ((rc = get_ctx(-1, c))) return rc;
     ScratchOrder order(*c, (hipStream_t)stream);        // the band, the table and the wrapped map are the context's
-    return ftp_launch(*c, d_img_obj, ch_obj, d_img_ref, ch_ref, h, w, fmin, fmax, unwrap, tau, d_out, (hipStream_t)stream);
+    return ftp_dft_launch(*c, 2, d_img_obj, ch_obj, d_img_ref, ch_ref, h, w, fmin, fmax, unwrap, tau, d_out, (hipStream_t)stream);
+}
+
+// one image (include/ssamd_ftp_mapping.h): the checks of the pair with the one channel count twice
+int ssamd_ftp_carrier_phase(const uint8_t *img, int ch, int h, int w, const double *fmin, const double *fmax, int unwrap, double tau,
+                            double *out, int device)
+{
+    if (!img || !out) return fail(SSAMD_EINVAL, "NULL buffer");
+    int rc = ftp_check(ch, ch, h, w, fmin, fmax, unwrap, tau);
+    if (rc) return rc;
+    const size_t px = (size_t)h * w;
+    return host_route(device, {{&Ctx::imgL, img, px * ch}}, {&Ctx::uwOut, out, px * sizeof(double)}, [&](Ctx &c, hipStream_t s) {
+        return ftp_dft_launch(c, 1, (const uint8_t *)c.imgL.ptr, ch, nullptr, 0, h, w, fmin, fmax, unwrap, tau, (double *)c.uwOut.ptr, s);
+    });
+}
+
+int ssamd_ftp_carrier_phase_device(const uint8_t *d_img, int ch, int h, int w, const double *fmin, const double *fmax, int unwrap,
+                                   double tau, double *d_out, void *stream)
+{
+    if (!d_img || !d_out) return fail(SSAMD_EINVAL, "NULL buffer");
+    int rc = ftp_check(ch, ch, h, w, fmin, fmax, unwrap, tau);
+    if (rc) return rc;
+    CtxLock c;
+    if ((rc = get_ctx(-1, c))) return rc;
+    ScratchOrder order(*c, (hipStream_t)stream);        // the band, the table and the wrapped map are the context's
+    return ftp_dft_launch(*c, 1, d_img, ch, nullptr, 0, h, w, fmin, fmax, unwrap, tau, d_out, (hipStream_t)stream);
 }
 }  // extern "C"

@@ -35,20 +35,11 @@ int graycode_decode_check(const void *planes, int n, int hc, int wc, const void 
     return SSAMD_OK;
 }
 
-// the entries of the FTP cloud geometry the triangulation reads: [12..36] and [40..67]; the others stay 0
+// the entries of the FTP cloud geometry the triangulation reads (ftp_load_geom, host_ftp_cloud.h)
 int graycode_geom_check(const double *geom, FtpCloudGeom &G, int &model)
 {
     if (!geom) return fail(SSAMD_EINVAL, "NULL buffer");
-    double g[SSAMD_FTP_CLOUD_NGEOM] = {0};
-    for (int i = 12; i < SSAMD_FTP_CLOUD_NGEOM; ++i) {
-        if (i >= 37 && i < 40) continue;
-        if (!std::isfinite(geom[i])) return fail(SSAMD_EINVAL, "geom[%d] is not finite", i);
-        g[i] = geom[i];
-    }
-    std::memcpy(&G, g, sizeof(G));
-    auto any = [&](int a, int b) { for (int i = a; i < b; ++i) if (G.d[i] != 0) return true; return false; };
-    model = any(8, 12) ? 3 : any(5, 8) ? 2 : any(0, 5) ? 1 : 0;
-    return SSAMD_OK;
+    return ftp_load_geom(geom, {{12, 37}, {40, SSAMD_FTP_CLOUD_NGEOM}}, G, model);
 }
 
 int graycode_decode_launch(Ctx &c, const uint8_t *d_planes, int hc, int wc, const float *d_mapx, const float *d_mapy, int x0, int y0, int w,

@@ -75,6 +75,45 @@ def test_device_tensors_against_truth_and_equal_to_host(active, data, name):
     assert _bitwise(got, active.ftpPhase(obj, ref, fc, rf))
 
 
+# The pair kernel at each columns-per-thread instance the fixture does not reach (it holds CPT 1 and, with max_width, 8): the
+# smallest width of CPT 2, 4 and 8 (ftp_plan.h), two rows and a narrow band -- the shapes of the one-image cases cpt2_w1025,
+# cpt4_w2049 and cpt8_w4097 of tests/golden/ftp_mapping_cases.  name: (w, radius_factor); fc is the frequency nearest to 0.05
+# with a whole number of fringes in the row, so that no pixel at the row's ends has a small |ghat * conj(g0hat)|.
+CPT_CASES = {"cpt2_w1025": (1025, 0.1), "cpt4_w2049": (2049, 0.05), "cpt8_w4097": (4097, 0.03)}
+_CPT = {}
+
+
+def _cpt_case(name):
+    """-> (obj, ref, fc, radius_factor, truth, numpy_err, tol): the fixture's rule applied here, once -- the inputs chosen so
+    that no pixel's angle is ill-conditioned, the tolerance from numpy's own distance to the extended-precision truth"""
+    if name not in _CPT:
+        import make_golden_ftp
+        w, rf = CPT_CASES[name]
+        fc = round(0.05 * w) / w
+        obj, ref = make_golden_ftp.fringes(2, w, fc, seed=w)
+        truth, ratio = _ftp_ref.truth_longdouble(obj, ref, fc, rf)
+        assert ratio.min() >= META["min_ratio"], (name, float(ratio.min()))
+        numpy_err = float(_ftp_ref.wrap_err(_ftp_ref.ftp_phase_numpy(obj, ref, fc, rf), truth).max())
+        truth.setflags(write=False)
+        _CPT[name] = (obj, ref, fc, rf, truth, numpy_err, META["tol_factor"] * max(numpy_err, META["tol_floor"]))
+    return _CPT[name]
+
+
+@pytest.mark.parametrize("name", sorted(CPT_CASES))
+def test_pair_kernel_at_each_columns_per_thread_host_and_device(active, name):
+    import torch
+    obj, ref, fc, rf, truth, numpy_err, tol = _cpt_case(name)
+    host = active.ftpPhase(obj, ref, fc, rf)
+    dev = active.ftpPhase(torch.from_numpy(obj).cuda(), torch.from_numpy(ref).cuda(), fc, rf)
+    assert dev.is_cuda and dev.dtype == torch.float64
+    for form, got in (("host", host), ("device", dev.cpu().numpy())):
+        assert got.dtype == np.float64 and got.shape == truth.shape and np.isfinite(got).all()
+        err = _ftp_ref.wrap_err(got, truth)
+        print("%s, %s form: worst angle error %.3e (numpy %.3e, tolerance %.3e)" % (name, form, float(err.max()), numpy_err, tol))
+        assert float(err.max()) <= tol, (name, form, float(err.max()), tol, np.unravel_index(int(err.argmax()), err.shape))
+    assert _bitwise(dev.cpu().numpy(), host)
+
+
 def test_scalar_fc_and_python_numbers(active, data):
     obj, ref, fc, rf = _inputs(data, "w97")
     a = active.ftpPhase(obj, ref, fc, rf)

@@ -205,6 +205,25 @@ def test_mapping_cloud_equals_the_restatement(ss, h, w, roi_xy):
     assert np.isfinite(want).all()
 
 
+@pytest.mark.parametrize("h,w", [(1, 1), (5, 1), (2, 64), (1, 129), (3, 43)])
+def test_shared_frame_through_both_cloud_kernels(ss, h, w):
+    """ftp_cloud_frame, the frame ftp_mapping_cloud_kernel and ftp_cloud_kernel share, on the same shapes and a roi origin that is
+    not 0: a single pixel; every pair wrapping a row, with an odd tail; exactly one full round of a wave and no tail; a full round
+    plus a round of one pixel; 129 pixels with wraps in the middle of a pair.  Host and device results equal the two numpy
+    restatements bit for bit."""
+    import torch
+    params, roi = _rig_params("d8"), (571, 303, w, h)
+    want = _mapping_case(ss, params, _map_phase(h, w, seed=h * w) + 1200.0, roi, theta=1210.5)
+    assert np.isfinite(want).all()
+    G = ss.active.ftpGeometry(C.make_rig(ss, params), 1000.0, 12.0, roi)
+    phase = C.smooth_phase(h, w, 12.0, seed=h * w)
+    want = C.cloud_from_geometry(G.geom, phase, 2.0, roi[0], roi[1])
+    assert want.shape == (h, w, 3) and np.isfinite(want).all()
+    assert _same(ss.active.ftpCloud(phase, G, k=2.0), want)
+    dev = ss.active.ftpCloud(torch.from_numpy(phase).cuda(), G, k=2.0)
+    assert dev.is_cuda and _same(dev.cpu().numpy(), want)
+
+
 @pytest.mark.parametrize("dist", ["none", "d4", "d5", "d8", "d12"])
 def test_mapping_cloud_distortion_models(ss, dist):
     phase = _map_phase(4, 66, seed=3) + 1100.0
