@@ -344,7 +344,10 @@ int ssamd_ftp_cloud_device(const double *d_phase, int h, int w, int x0, int y0, 
 
 /* Raw left-referenced aggregated ASW costs, float32 [height][width][nD] with
  * nD = maxDisparity-minDisparity+1, NaN where the reference evaluates no
- * candidate (x-d < 0).  Host buffers, synchronous.  For tolerance tests. */
+ * candidate (x-d < 0).  Host buffers, synchronous.  For tolerance tests.
+ * Test hook SSAMD_ASW_COST_KEYS=1: the array holds, as bit patterns, the 32-bit
+ * cost images the winner-take-all compares (cost <= 20: the float's bits, above:
+ * 0xC0000000 - bits(40 - cost)), and 0xFFFFFFFF where there is no candidate. */
 int ssamd_asw_costs(const uint8_t *img1, const uint8_t *img2, int height, int width,
                     int winSize, int maxDisparity, int minDisparity,
                     double gammaC, double gammaP, float *costs, int device);

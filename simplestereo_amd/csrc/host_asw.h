@@ -345,7 +345,7 @@ template <class Args> void asw_fill_args(Args &x, const AswRun &r, const AswGeom
     x.keyR = r.consistent ? (u64 *)r.c.keyR.ptr : nullptr;
     x.disp = direct ? r.d_disp : nullptr;
     x.costs = r.d_costs;
-    x.cost_keys = 0;
+    x.cost_keys = r.t.asw_cost_keys != 0;                             // (test hook: the dump holds the cost images)
     x.xq = r.xq_kernel;                                               // (the autotuner's trial launches run without the queue)
     x.evol = r.evol; x.erow0 = r.r0; x.erows = r.r1 - r.r0; x.evolW = r.evolW;
     x.H = r.H; x.W = r.W; x.win = r.win; x.pad = r.p; x.minD = r.minD; x.maxD = r.maxD; x.row0 = r.row0; x.rows = r.rows;

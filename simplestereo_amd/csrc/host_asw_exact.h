@@ -42,7 +42,11 @@ int asw_exact_prepare(Ctx &c, int W, int rows, int win, int nD, double gammaC, b
     // rounding of the Lab records to float (|dLab| <= ~1.3e-5 per colour distance), i.e. a relative error of ~2.6e-5 / gammaC on a
     // weight product -- scaled up for smaller gammaC; and the (N, S') sums are fp32 sums of win^2 products whose rounding errors
     // add up like a random walk (~win ulps): scaled up with the window beyond 35 (a fixed band ignored the tap
-    // count; tests/test_gpu_exact.py::test_large_windows_against_the_oracle)
+    // count; tests/test_gpu_exact.py::test_large_windows_against_the_oracle).
+    // MEASURED (profiles/exact_band_margin.txt, tests/test_gpu_asw_band.py): what the band has to cover is the error of the
+    // DIFFERENCE between the reference's winner and another candidate of the pixel, and their errors move together (shared left
+    // weights).  Worst line: 43 of 128 ulps in use (window 21, gammaC 5, gammaP 100), 23 of 128 at 35 / 5 / 17.5, under 5 % of
+    // the band wherever it is scaled up; half the band still reproduced every map of the canaries, a quarter did not.
     q.tol = (uint32_t)std::min(1.0e6, (double)tune().exact_tol * std::max(1.0, 5.0 / gammaC) * std::max(1.0, win / 35.0));
     // rounding noise of the reference's fp64 quotient sum(w e) / sum(w) over n = win^2 taps: <= ~(n + 3) u relative on numerator and
     // denominator each, u = 2^-53, i.e. 2 (n + 3) u 40 absolute near the cap; two candidates can swap places when they are

@@ -26,6 +26,7 @@
     X("SSAMD_ALT_QUEUE_CAP", alt_queue_cap, int, 0, std::max(1, atoi(v)), false)   /* 0 unset */ \
     X("SSAMD_AUTOTUNE", autotune_env, int, -2, atoi(v) > 0 ? 1 : (atoi(v) < 0 ? -1 : 0), false)   /* -2 unset */ \
     X("SSAMD_ASW_EVOL_FAIL", evol_fail, int, 0, atoi(v), false)   /* test hook: 1 = the TAD volume's allocation really fails (a hipMalloc no device can serve) */ \
+    X("SSAMD_ASW_COST_KEYS", asw_cost_keys, int, 0, atoi(v) != 0 ? 1 : 0, false)   /* test hook: 1 = ssamd_asw_costs returns the 32-bit cost images of asw_cost_key (bit patterns in the float array) instead of the costs; no kernel form changes */ \
     X("SSAMD_ASW_TAIL", asw_tail, int, -1, atoi(v), false)   /* -1: the host decides; 0: never split the last partial round of workgroups into half-width tiles; 1: whenever possible */ \
     X("SSAMD_ASW_PERSIST", asw_persist, int, -1, atoi(v), x > 0)   /* -1: the host decides; 0: the phase-shifted kernel always runs one workgroup per tile; n > 0: persistent form with min(n, resident slots) workgroups */ \
     X("SSAMD_ASW_PREPASS_FUSE", prepass_fuse, int, 1, atoi(v), false)   /* 0: Lab records and TAD volume as two dependent launches (the form of rounds 2-4) */ \

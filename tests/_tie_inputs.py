@@ -57,7 +57,62 @@ def patches(H, W, maxd, seed):
 GENERATORS = {"quantised": quantised, "black_margins": black_margins, "patches": patches}
 
 
+def shifted_noisy(H, W, maxd, seed):
+    """the recipe of tests/test_gpu_fuzz.py::_shifted_pair: low-contrast smooth texture and a shifted copy with noise of -2 .. 2
+    on every channel -- candidates are rarely saturated, and many lie a few cost-image ulps apart without tying exactly"""
+    rng = np.random.default_rng(seed)
+    L = make_pair(H, W, 8, seed)[0]
+    L = (110 + (L.astype(np.int32) - 128) // 6).astype(np.uint8)
+    d0 = int(rng.integers(0, max(0, min(maxd, W // 2)) + 1))
+    R = np.roll(L, -d0, axis=1).astype(np.int32) + rng.integers(-2, 3, size=L.shape)
+    return np.ascontiguousarray(L), np.ascontiguousarray(np.clip(R, 0, 255).astype(np.uint8))
+
+
+def stripes(H, W, maxd, seed):
+    """every row one colour (a textureless scene: all candidates of a pixel see the same windows), the right view one level
+    brighter in one channel: every tap has TAD 1 and every candidate away from the left border costs exactly 1.  For
+    `perturbed`: a step in a row of another colour moves a cost by that row's (small) weight -- near-ties that are not exact"""
+    rng = np.random.default_rng(seed)
+    rows = rng.integers(8, 248, (H, 1, 3))
+    L = np.ascontiguousarray(np.broadcast_to(rows, (H, W, 3)).astype(np.uint8))
+    R = L.copy()
+    R[:, :, rng.integers(0, 3)] += 1
+    return L, R
+
+
+def soft_stripes(H, W, maxd, seed):
+    """stripes whose row colours are a random walk of up to 12 levels per channel and row: neighbouring rows lie a few Lab
+    units apart, so that at gammaC = 0.7 (where a row of stripes()'s colours weighs 1e-60) a step in the next row still moves a cost"""
+    rng = np.random.default_rng(seed)
+    rows = np.clip(128 + np.cumsum(rng.integers(-12, 13, (H, 1, 3)), axis=0), 8, 247)
+    L = np.ascontiguousarray(np.broadcast_to(rows, (H, W, 3)).astype(np.uint8))
+    R = L.copy()
+    R[:, :, rng.integers(0, 3)] += 1
+    return L, R
+
+
+GENERATORS["shifted_noisy"] = shifted_noisy
+GENERATORS["stripes"] = stripes
+GENERATORS["soft_stripes"] = soft_stripes
+
+
+def perturbed(kind, H, W, maxd, seed, share=0.02):
+    """generator `kind` with +-1 on one channel of about 2 % of the right view's pixels: its exact ties (identical windows, whose
+    fp32 and fp64 costs differ by the same amount) become near-ties that are not exact"""
+    L, R = GENERATORS[kind](H, W, maxd, seed)
+    rng = np.random.default_rng(seed + 7919)
+    ys, xs = np.nonzero(rng.random((H, W)) < share)
+    ch = rng.integers(0, 3, ys.size)
+    step = rng.integers(0, 2, ys.size) * 2 - 1
+    R = R.astype(np.int32)
+    R[ys, xs, ch] += step
+    return L, np.ascontiguousarray(np.clip(R, 0, 255).astype(np.uint8))
+
+
 def pair(kind, H, W, maxd, seed=1):
+    """`kind`: a generator's name, or "perturbed:<name>" """
+    if kind.startswith("perturbed:"):
+        return perturbed(kind.split(":", 1)[1], H, W, maxd, seed)
     return GENERATORS[kind](H, W, maxd, seed)
 
 
