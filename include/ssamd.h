@@ -142,8 +142,11 @@ int ssamd_gsw_device_rows2(const uint8_t *d_img1, const uint8_t *d_img2, int hei
  * gammaC = 5 / winSize <= 35, wider for smaller gammaC and larger windows; on the saturated side within the reference's own fp64
  * rounding noise, ~6 win^2 2^-53 40 absolute), re-evaluate the queue in fp64 -- the reference's expression and summation order
  * (_passive.cpp:37-50, 57-88), fp64 CIELab (colorconversion.hpp:67-69), no contraction -- and redo those argmins (first minimum
- * wins, :90-93 / 243-246); both the left- and the right-referenced pass with `consistent`.  Scratch: O(H*W) (fp64 Lab images
- * 48 B / pixel, queue and slots 40 B / pixel; round 5 needed H*W*nD*4 bytes).  The weights are the reference's to the bit (glibc's
+ * wins, :90-93 / 243-246); both the left- and the right-referenced pass with `consistent`.  Scratch: O(H*W) -- fp64 Lab images 48 B / pixel,
+ * queue and costs 16 B for each of max(4 per pixel, min(every candidate twice, 2^23)) entries (at most 2^26), result slots 32 B / pixel,
+ * flags 4 B / pixel, weight tables up to 64 MiB, and for consistent / multi-chunk calls a raw queue of 12 B for each of
+ * max(2 per pixel, min(every candidate twice, 2^23)) entries: about 375 MB at 1080p (475 MB consistent), 1.4 GB at 4096 x 2160;
+ * round 5 needed H*W*nD*4 bytes.  The weights are the reference's to the bit (glibc's
  * exp and powf restated for the device, csrc/glibc_math.hip.h; IEEE sqrt and division), so candidates one ulp apart resolve as in
  * the reference too: on the goldens, the whole bench frames and 77 000 random frames (rounds 5 and 6) the map IS the reference's.  Among exactly
  * equal fp64 costs the smallest index wins, as in ssamd_asw.  Candidates whose fp32 cost is exactly 0 are not queued: pixels with two

@@ -30,33 +30,67 @@
 // more than the near-tie band from their winner although it wins in fp64 (none seen; the band grows with the window,
 // host_asw_exact.h), and a queue overflow (counted, reported, the fp32 map is kept).
 #pragma once
+#include <type_traits>
 #include "asw_shared.hip.h"
 #include "lab_kernels.hip.h"
 #include "glibc_math.hip.h"
 
 namespace ssamd {
 
+// Per-side buffers are arrays of two: [0] = the left-referenced winners (anchor pixels are left pixels), [1] = the right-referenced
+// ones of a `consistent` call (anchor pixels are right pixels).  A side's bit in an entry's `sides` is EXACT_SIDE_L << side, its pixel
+// flags are q.flagL / q.flagR.  The kernels below state each step ONCE, for a side; exact_each_side runs it.
 struct AswExactArgs {
-    const PixRec *recL, *recR;       // [H][W] records (bgrx = the raw bytes)
-    const double *labL, *labR;       // [H][W][3] fp64 CIELab (rows the call touches)
+    const PixRec *rec[2];            // [H][W] records of the left / right image (bgrx = the raw bytes)
+    const double *lab[2];            // [H][W][3] fp64 CIELab of them (rows the call touches)
     const double *prox;              // [win*win] fp64 proximity weights
-    u64 *keyL, *keyR;                // [rows][W] WTA keys of the aggregation (keyL null: `disp` holds the left winners; keyR may be null)
-    int16_t *disp;                   // [rows][W] the map the aggregation kernel wrote itself (keyL == nullptr)
-    AswExactQueue q;                 // queue, counter (q.counter[0]; [1] / [2]: flagged left / right pixels), pixel flags
+    u64 *keys[2];                    // [rows][W] WTA keys of the aggregation ([0] null: `disp` holds the left winners; [1] null: no right pass)
+    int16_t *disp;                   // [rows][W] the map the aggregation kernel wrote itself (keys[0] == nullptr)
+    AswExactQueue q;                 // final queue and pixel flags; q.counter = the counter block (ExactCounter)
     AswExactQueue raw;               // MERGING calls: what the aggregation kernels selected against tile-local winners, with cost images
                                      //   (raw.entries == nullptr: a direct call, the kernels filled q themselves)
     double *ecost;                   // [cap] fp64 cost of each entry
-    u64 *costL, *costR;              // [rows][W] minimum fp64 cost bits over the pixel's entries (initialised for flagged pixels)
-    uint32_t *idxL, *idxR;           // [rows][W] smallest index among the entries at that minimum
+    u64 *cost[2];                    // [rows][W] minimum fp64 cost bits over the pixel's entries (initialised for flagged pixels)
+    uint32_t *idx[2];                // [rows][W] smallest index among the entries at that minimum
     // weight tables of flagged pixels (asw_exact_wtab_kernel): the ~180 queue entries of a flagged left pixel share their LEFT support
     // weights (w1 depends on the left pixel only, _passive.cpp:47-50), those of a flagged right pixel their right ones
-    uint32_t *wslotL, *wslotR;       // [rows][W] table slot of a flagged pixel (written for flagged pixels only; >= wcap: none)
+    uint32_t *wslot[2];              // [rows][W] table slot of a flagged pixel (written for flagged pixels only; >= wcap: none)
     uint32_t *wpix;                  // [wcap] pixel | side << 31 of each slot
     double *wtab;                    // [wcap][win * win] prox * exp(-dLab / gammaC) towards the slot's centre pixel, 0 outside the image
-    unsigned int wcap;               // slots available (counter[6] = slots asked for)
+    unsigned int wcap;               // slots available (counter EXACT_CTR_WSLOTS = slots asked for)
     int H, W, win, pad, minD, maxD, row0, rows;
     double gammaC;
 };
+
+// f(side) with `side` a compile-time constant (usable as a template argument): the left side and, if there is a right pass, the right one
+template <typename F>
+__device__ __forceinline__ void exact_each_side(const AswExactArgs &A, F f)
+{
+    f(std::integral_constant<int, 0>{});
+    if (A.keys[1]) f(std::integral_constant<int, 1>{});
+}
+
+// ---- what differs between the sides: one index mapping.  An entry (pix, d) names the LEFT pixel pix and the right pixel pix - d.
+// Side 0 anchors it at the left pixel and ranks it by d; side 1 anchors it at the right pixel and ranks it by the left column.
+template <int S> __device__ __forceinline__ uint32_t exact_anchor(const ExactEntry &e) { return S ? e.pix - (uint32_t)e.d : e.pix; }
+template <int S> __device__ __forceinline__ uint32_t exact_windex(const ExactEntry &e, int W) { return S ? e.pix % (uint32_t)W : (uint32_t)e.d; }
+
+// EVERY candidate of anchor pixel q (column x) but its winner `widx` goes to the final queue (asw_exact_winners_kernel adds the
+// winner): d = minD .. maxD with the other image's column inside it -- x - d >= 0 on the left, x + d < W on the right (_passive.cpp:56)
+template <int S>
+__device__ __forceinline__ void exact_queue_all_candidates(const AswExactArgs &A, long long q, int x, int widx)
+{
+    const AswExactQueue &Q = A.q;
+    const int dhi = min(A.maxD, S ? A.W - 1 - x : x), cnt = dhi - A.minD;
+    if (cnt <= 0) return;
+    unsigned slot = atomicAdd(Q.counter, (unsigned)cnt);
+    for (int d = A.minD; d <= dhi; ++d)
+        if ((S ? x + d : d) != widx) {
+            if (slot < Q.cap) Q.entries[slot] = exact_entry((uint32_t)(S ? q + d : q), d, EXACT_SIDE_L << S);
+            ++slot;
+        }
+    (S ? Q.flagR : Q.flagL)[q] = 1;
+}
 
 // sqrt as the host computes it (IEEE, correctly rounded): the device's f64 square root (v_rsq_f64 + Goldschmidt steps) is within an
 // ulp but not always the correctly rounded one; with the exact residual e = x - y0^2 (one fma) the root is y0 + e / (2 y0) up to
@@ -68,6 +102,18 @@ __device__ __forceinline__ double exact_sqrt(double x)
     if (!(y0 > 0.0) || !(y0 < 1.0e300)) return y0;                   // 0, nan, inf
     const double e = fma(-y0, y0, x);
     return y0 + e / (2.0 * y0);
+}
+
+// The reference's support weight of the tap (row, col) of `lab` towards a centre of colour (c0, c1, c2): prox * exp(-dLab / gammaC)
+// (_passive.cpp:47-50).  The ONE statement of it: the weight tables and the per-entry evaluation both call this function, so a
+// table holds the bits the evaluation would compute.  exp_tab = glibc's table (gm_exp_tab), in LDS.
+__device__ __forceinline__ double exact_weight(const double *lab, double c0, double c1, double c2, int row, int col, int W, double prox,
+                                               double gammaC, const uint64_t *exp_tab)
+{
+#pragma clang fp contract(off)
+    const double *const t = lab + 3 * ((size_t)row * W + col);
+    const double a0 = t[0] - c0, a1 = t[1] - c1, a2 = t[2] - c2;
+    return prox * glibc_exp_t(-exact_sqrt(a0 * a0 + a1 * a1 + a2 * a2) / gammaC, exp_tab);
 }
 
 // fp64 Lab of the rows [r0, r0 + npix / W) from the records' bytes, both images in one launch
@@ -91,37 +137,32 @@ __global__ __launch_bounds__(256) void bgr2lab_f64_pair_kernel(const PixRec *__r
 // has a queue of this call overflowed?  (then candidate sets are incomplete: every later kernel of the pass returns, the fp32 map stays)
 __device__ __forceinline__ bool exact_overflowed(const AswExactArgs &A)
 {
-    return A.q.counter[0] > A.q.cap || (A.raw.entries && A.raw.counter[0] > A.raw.cap);
+    return exact_count(A.q) > A.q.cap || (A.raw.entries && exact_count(A.raw) > A.raw.cap);
 }
 
-// 1b. MERGING calls: the raw candidates against the FINAL winners.  keyL == nullptr cannot happen here (direct calls have no raw queue).
+// 1b. MERGING calls: the raw candidates against the FINAL winners.  (Direct calls have no raw queue: both sides have keys here.)
 __global__ __launch_bounds__(256) void asw_exact_filter_kernel(const AswExactArgs A)
 {
-    const unsigned n = min(A.raw.counter[0], A.raw.cap);
+    const unsigned n = min(exact_count(A.raw), A.raw.cap);
     const unsigned nloop = (n + 255u) & ~255u;                          // uniform trip counts: the push is wave-aggregated
     for (unsigned e0 = blockIdx.x * blockDim.x; e0 < nloop; e0 += gridDim.x * blockDim.x) {
         const unsigned e = e0 + threadIdx.x;
         unsigned s2 = 0;
-        uint32_t pix = 0, rkey = 0xffffffffu;
-        int d = 0;
+        ExactEntry en{};
+        uint32_t rkey = 0xffffffffu;
         if (e < n) {
-            const u64 ent = A.raw.entries[e];
-            const uint32_t key = A.raw.ekeys[e];
-            rkey = key;
-            pix = (uint32_t)ent;
-            d = (int)((ent >> 32) & 0xffff);
-            const unsigned sides = (unsigned)(ent >> 48) & 3u;
-            const uint32_t esc = 0xC0000000u - __float_as_uint(2.0f * A.q.sat_abs);      // (escalated pixels get every candidate from asw_exact_escalate_kernel)
-            if (sides & EXACT_SIDE_L) {
-                const u64 g = A.keyL[pix];
-                if ((int)(uint32_t)g != d && (uint32_t)(g >> 32) < esc && exact_near(key, (uint32_t)(g >> 32), A.q.tol, A.q.sat_abs, exact_zkey(A.win))) s2 |= EXACT_SIDE_L;
-            }
-            if ((sides & EXACT_SIDE_R) && A.keyR) {
-                const u64 g = A.keyR[pix - (uint32_t)d];
-                if ((uint32_t)g != pix % (uint32_t)A.W && (uint32_t)(g >> 32) < esc && exact_near(key, (uint32_t)(g >> 32), A.q.tol, A.q.sat_abs, exact_zkey(A.win))) s2 |= EXACT_SIDE_R;
-            }
+            en = exact_decode(A.raw.entries[e]);
+            rkey = A.raw.ekeys[e];
+            const uint32_t esc = asw_inv_key(2.0f * A.q.sat_abs);          // (escalated pixels get every candidate from asw_exact_escalate_kernel)
+            exact_each_side(A, [&](auto side) {
+                if (!(en.sides & (EXACT_SIDE_L << side))) return;
+                const u64 g = A.keys[side][exact_anchor<side>(en)];
+                if ((uint32_t)g != exact_windex<side>(en, A.W) && (uint32_t)(g >> 32) < esc &&
+                    exact_near(rkey, (uint32_t)(g >> 32), A.q.tol, A.q.sat_abs, exact_zkey(A.win)))
+                    s2 |= EXACT_SIDE_L << side;
+            });
         }
-        asw_exact_push_wave(A.q, s2 != 0, pix, d, s2, rkey);
+        asw_exact_push_wave(A.q, s2 != 0, en.pix, en.d, s2, rkey);
     }
 }
 
@@ -130,41 +171,14 @@ __global__ __launch_bounds__(256) void asw_exact_filter_kernel(const AswExactArg
 // be the reference's first minimum here.  One thread per pixel; rare (occlusions, noise).
 __global__ __launch_bounds__(256) void asw_exact_escalate_kernel(const AswExactArgs A)
 {
-    const AswExactQueue &Q = A.q;
-    const uint32_t esc = 0xC0000000u - __float_as_uint(2.0f * Q.sat_abs);      // images at or above: 40 - cost <= 2 sat_abs
+    const uint32_t esc = asw_inv_key(2.0f * A.q.sat_abs);                  // images at or above: 40 - cost <= 2 sat_abs
     const long long n = (long long)A.rows * A.W;
     for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (long long)gridDim.x * blockDim.x) {
         const int x = (int)(q % A.W);
-        const u64 gl = A.keyL[q];
-        if (gl != KEY_NONE && (uint32_t)(gl >> 32) >= esc) {
-            const int dwin = (int)(uint32_t)gl, dhi = min(A.maxD, x);            // candidates d = minD .. min(maxD, x) (_passive.cpp:56)
-            const int cnt = dhi - A.minD;                                       // all but the winner (asw_exact_winners_kernel adds it)
-            if (cnt > 0) {
-                unsigned slot = atomicAdd(Q.counter, (unsigned)cnt);
-                for (int d = A.minD; d <= dhi; ++d)
-                    if (d != dwin) {
-                        if (slot < Q.cap) Q.entries[slot] = exact_entry((uint32_t)q, d, EXACT_SIDE_L);
-                        ++slot;
-                    }
-                Q.flagL[q] = 1;
-            }
-        }
-        if (A.keyR) {
-            const u64 gr = A.keyR[q];
-            if (gr != KEY_NONE && (uint32_t)(gr >> 32) >= esc) {
-                const int xwin = (int)(uint32_t)gr;                              // right pixel x: left columns x + d, d = minD .. maxD, below W
-                const int dhi = min(A.maxD, A.W - 1 - x), cnt = dhi - A.minD;
-                if (cnt > 0) {
-                    unsigned slot = atomicAdd(Q.counter, (unsigned)cnt);
-                    for (int d = A.minD; d <= dhi; ++d)
-                        if (x + d != xwin) {
-                            if (slot < Q.cap) Q.entries[slot] = exact_entry((uint32_t)(q + d), d, EXACT_SIDE_R);
-                            ++slot;
-                        }
-                    Q.flagR[q] = 1;
-                }
-            }
-        }
+        exact_each_side(A, [&](auto side) {
+            const u64 g = A.keys[side][q];
+            if (g != KEY_NONE && (uint32_t)(g >> 32) >= esc) exact_queue_all_candidates<side>(A, q, x, (int)(uint32_t)g);
+        });
     }
 }
 
@@ -197,7 +211,7 @@ __global__ __launch_bounds__(256) void asw_exact_zero_kernel(const AswExactArgs 
     for (long long seg = blockIdx.x; seg < (long long)A.rows * segs_per_row; seg += gridDim.x) {
         const int yr = (int)(seg / segs_per_row), x0 = (int)(seg - (long long)yr * segs_per_row) * EXACT_ZSEG, y = A.row0 + yr;
         if (!Q.zrow[yr]) continue;                                      // no tile-local winner of this row costs exactly 0 (the usual case)
-        for (int side = 0; side < (A.keyR ? 2 : 1); ++side) {
+        for (int side = 0; side < (A.keys[1] ? 2 : 1); ++side) {
             __syncthreads();
             if (tid < EXACT_ZSEG) {
                 const int x = x0 + tid;
@@ -208,12 +222,12 @@ __global__ __launch_bounds__(256) void asw_exact_zero_kernel(const AswExactArgs 
                     if (side == 0) {                                    // marked by the aggregation kernels: two or more zero-cost candidates
                         z = Q.zeroL[q] != 0;
                         if (z) {
-                            if (A.keyL) { const u64 g = A.keyL[q]; z = g != KEY_NONE && (uint32_t)(g >> 32) == 0u; idx = (int)(uint32_t)g; }
+                            if (A.keys[0]) { const u64 g = A.keys[0][q]; z = g != KEY_NONE && (uint32_t)(g >> 32) == 0u; idx = (int)(uint32_t)g; }
                             else idx = (int)A.disp[q];
                         }
                     } else {
                         z = Q.zeroR[q] != 0;
-                        if (z) { const u64 g = A.keyR[q]; z = g != KEY_NONE && (uint32_t)(g >> 32) == 0u; idx = (int)(uint32_t)g; }
+                        if (z) { const u64 g = A.keys[1][q]; z = g != KEY_NONE && (uint32_t)(g >> 32) == 0u; idx = (int)(uint32_t)g; }
                     }
                 }
                 s_idx[tid] = idx;
@@ -223,7 +237,7 @@ __global__ __launch_bounds__(256) void asw_exact_zero_kernel(const AswExactArgs 
             if (win >= EXACT_ZWIN_MAX) {                                // (LDS tiles sized for windows below 64: larger ones are re-evaluated in fp64)
                 if (tid < EXACT_ZSEG && s_state[tid] == 1) s_state[tid] = 3;
             } else {
-                const PixRec *const imgA = side ? A.recR : A.recL, *const imgB = side ? A.recL : A.recR;
+                const PixRec *const imgA = side ? A.rec[1] : A.rec[0], *const imgB = side ? A.rec[0] : A.rec[1];
                 // (tiles are staged eight loads at a time: one load per loop trip serialises on the HBM latency -- a first form spent 1.2 ms here)
                 auto stage = [&](uint32_t *tile, const PixRec *img, int shift) {
                     for (int k0 = 0; k0 < win * TW; k0 += 8 * 256) {
@@ -305,18 +319,19 @@ __global__ __launch_bounds__(256) void asw_exact_zero_kernel(const AswExactArgs 
 }
 
 // a weight-table slot for every flagged pixel of the wave (mask = ballot(flagged)): one atomic per wave
-__device__ __forceinline__ void exact_assign_wslot(const AswExactArgs &A, bool flagged, u64 mask, uint32_t pix, uint32_t side)
+template <int S>
+__device__ __forceinline__ void exact_assign_wslot(const AswExactArgs &A, bool flagged, u64 mask, uint32_t pix)
 {
     if (mask == 0 || A.wcap == 0) return;
     const int leader = (int)__builtin_ctzll(mask);
     const unsigned lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     unsigned base = 0;
-    if ((int)lane == leader) base = atomicAdd(A.q.counter + 6, (unsigned)__builtin_popcountll(mask));
+    if ((int)lane == leader) base = atomicAdd(A.q.counter + EXACT_CTR_WSLOTS, (unsigned)__builtin_popcountll(mask));
     base = (unsigned)__builtin_amdgcn_readlane((int)base, leader);
     if (flagged) {
         const unsigned slot = base + (unsigned)__builtin_popcountll(mask & (((u64)1 << lane) - 1));
-        (side ? A.wslotR : A.wslotL)[pix] = slot;
-        if (slot < A.wcap) A.wpix[slot] = pix | (side << 31);
+        A.wslot[S][pix] = slot;
+        if (slot < A.wcap) A.wpix[slot] = pix | ((uint32_t)S << 31);
     }
 }
 
@@ -329,61 +344,46 @@ __global__ __launch_bounds__(256) void asw_exact_winners_kernel(const AswExactAr
     for (long long q0 = (long long)blockIdx.x * blockDim.x; q0 < n; q0 += (long long)gridDim.x * blockDim.x) {
         const long long q = q0 + threadIdx.x;
         const bool inb = q < n;
-        const bool fl = inb && Q.flagL[q];
-        if (fl) {
-            A.costL[q] = ~0ull;
-            A.idxL[q] = 0xffffffffu;
-        }
-        const int dwin = fl ? (A.keyL ? (int)(uint32_t)A.keyL[q] : (int)A.disp[q]) : 0;
-        const u64 ml = __builtin_amdgcn_ballot_w64(fl);
-        if (ml && fl && (int)__builtin_ctzll(ml) == (int)(threadIdx.x & 63)) atomicAdd(Q.counter + 1, (unsigned)__builtin_popcountll(ml));
-        exact_assign_wslot(A, fl, ml, (uint32_t)q, 0u);
-        asw_exact_push_wave(Q, fl, (uint32_t)q, dwin, EXACT_SIDE_L, fl && A.keyL ? (uint32_t)(A.keyL[q] >> 32) : 0xffffffffu);
-        if (A.keyR) {
-            const bool fr = inb && Q.flagR[q];
-            int xl = 0, xr = 0;
-            if (fr) {
-                A.costR[q] = ~0ull;
-                A.idxR[q] = 0xffffffffu;
-                xr = (int)(q % A.W);
-                xl = (int)(uint32_t)A.keyR[q];
+        exact_each_side(A, [&](auto side) {
+            u64 *const keys = A.keys[side];
+            const bool f = inb && (side ? Q.flagR : Q.flagL)[q];
+            int d = 0;
+            if (f) {
+                A.cost[side][q] = ~0ull;
+                A.idx[side][q] = 0xffffffffu;
+                d = (keys ? (int)(uint32_t)keys[q] : (int)A.disp[q]) - (side ? (int)(q % A.W) : 0);      // (right: the winner is a left column; no keys: a direct call)
             }
-            const u64 mr = __builtin_amdgcn_ballot_w64(fr);
-            if (mr && fr && (int)__builtin_ctzll(mr) == (int)(threadIdx.x & 63)) atomicAdd(Q.counter + 2, (unsigned)__builtin_popcountll(mr));
-            exact_assign_wslot(A, fr, mr, (uint32_t)q, 1u);
-            asw_exact_push_wave(Q, fr, (uint32_t)(q + (xl - xr)), xl - xr, EXACT_SIDE_R, fr ? (uint32_t)(A.keyR[q] >> 32) : 0xffffffffu);
-        }
+            const u64 m = __builtin_amdgcn_ballot_w64(f);
+            if (m && f && (int)__builtin_ctzll(m) == (int)(threadIdx.x & 63))
+                atomicAdd(Q.counter + (side ? EXACT_CTR_FLAGGED_R : EXACT_CTR_FLAGGED_L), (unsigned)__builtin_popcountll(m));
+            exact_assign_wslot<side>(A, f, m, (uint32_t)q);
+            asw_exact_push_wave(Q, f, (uint32_t)(side ? q + d : q), d, EXACT_SIDE_L << side, f && keys ? (uint32_t)(keys[q] >> 32) : 0xffffffffu);
+        });
     }
 }
 
 // 2b. the support weights of every flagged pixel towards its window, once: prox * exp(-dLab / gammaC) in the reference's expression
-// (_passive.cpp:47-50) -- the same instructions on the same operands as asw_exact_eval_kernel would execute per entry, so the same bits.
-// One wave per table slot.
+// (_passive.cpp:47-50) -- by exact_weight, the function asw_exact_eval_kernel calls per entry where there is no table: the same bits
+// by construction.  One wave per table slot.
 __global__ __launch_bounds__(256) void asw_exact_wtab_kernel(const AswExactArgs A)
 {
-#pragma clang fp contract(off)
     __shared__ uint64_t s_exp[256];
     for (int k = threadIdx.x; k < 256; k += blockDim.x) s_exp[k] = gm_exp_tab[k];
     __syncthreads();
     if (exact_overflowed(A)) return;
-    const unsigned n = min(A.q.counter[6], A.wcap);
+    const unsigned n = min(A.q.counter[EXACT_CTR_WSLOTS], A.wcap);
     const int lane = threadIdx.x & 63, W = A.W, H = A.H, win = A.win, p = A.pad, win2 = win * win;
     for (unsigned slot = blockIdx.x * 4 + (threadIdx.x >> 6); slot < n; slot += gridDim.x * 4) {
         const uint32_t pw = A.wpix[slot], pix = pw & 0x7fffffffu;
-        const double *const lab = (pw >> 31) ? A.labR : A.labL;
+        const double *const lab = (pw >> 31) ? A.lab[1] : A.lab[0];
         const int yr = (int)(pix / (uint32_t)W), x = (int)(pix - (uint32_t)yr * (uint32_t)W), y = A.row0 + yr;
         const double *const c = lab + 3 * ((size_t)y * W + x);
         const double c0 = c[0], c1 = c[1], c2 = c[2];
         double *const out = A.wtab + (size_t)slot * win2;
         for (int t = lane; t < win2; t += 64) {
             const int i = t / win, j = t - i * win, ii = y - p + i, cc = x - p + j;
-            double w = 0.0;
-            if ((unsigned)ii < (unsigned)H && (unsigned)cc < (unsigned)W) {
-                const double *const tp = lab + 3 * ((size_t)ii * W + cc);
-                const double a0 = tp[0] - c0, a1 = tp[1] - c1, a2 = tp[2] - c2;
-                w = A.prox[t] * glibc_exp_t(-exact_sqrt(a0 * a0 + a1 * a1 + a2 * a2) / A.gammaC, s_exp);
-            }
-            out[t] = w;
+            const bool inside = (unsigned)ii < (unsigned)H && (unsigned)cc < (unsigned)W;
+            out[t] = inside ? exact_weight(lab, c0, c1, c2, ii, cc, W, A.prox[t], A.gammaC, s_exp) : 0.0;
         }
     }
 }
@@ -397,7 +397,11 @@ __global__ __launch_bounds__(256) void asw_exact_wtab_kernel(const AswExactArgs 
 // load -> exp -> LDS -> serial-sum chain per row) and glibc's exp table in LDS instead of constant memory (two dependent global
 // loads per exp): 784 -> see profiles/r06_exact_mode_cost.txt for the 24 141 candidates of the bench frame.
 static constexpr int EXACT_WAVES = 4;          // entries in flight per workgroup
-static constexpr int EXACT_CHUNK = 256;        // taps per chunk and wave (4 KB of LDS: up to six waves per SIMD at 82 VGPRs)
+static constexpr int EXACT_CHUNK = 256;        // taps per chunk and wave (4 KB of LDS)
+// Workgroups per CU of the launch, = the workgroups a CU holds at once: the kernel compiles to 91 VGPRs, which the register file
+// hands out as 96, so 512 / 96 = 5 waves fit a SIMD and 4 SIMDs x 5 waves / EXACT_WAVES = 5 workgroups a CU (LDS, 18 KB a workgroup,
+// would allow 8).  Check tools/kernel_resources.sh ssamd_api.hip for occupancy 5 when the kernel or the compiler changes.
+static constexpr int EXACT_GROUPS_PER_CU = 5;
 __global__ __launch_bounds__(64 * EXACT_WAVES) void asw_exact_eval_kernel(const AswExactArgs A)
 {
 #pragma clang fp contract(off)
@@ -408,19 +412,16 @@ __global__ __launch_bounds__(64 * EXACT_WAVES) void asw_exact_eval_kernel(const 
     if (exact_overflowed(A)) return;               // queue overflow: incomplete candidate sets, the fp32 map is kept (asw_exact_patch_kernel)
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     double *const sw = s_w[wv], *const sc = s_c[wv];
-    const unsigned n = min(A.q.counter[0], A.q.cap);
+    const unsigned n = min(exact_count(A.q), A.q.cap);
     const int W = A.W, H = A.H, win = A.win, p = A.pad;
-    // static stride over a grid of exactly the waves the chip holds at once (the launcher sizes it: five 4-wave groups per CU): a larger
+    // static stride over a grid of exactly the waves the chip holds at once (the launcher sizes it: EXACT_GROUPS_PER_CU): a larger
     // grid left its last round of waves to run after the others had finished (6 144 waves for 5 120 slots: ~1.7 x the ideal time).
     // (Handing entries out through an atomic counter + readfirstlane hung the kernel on this compiler: not pursued.)
     for (unsigned e = blockIdx.x * EXACT_WAVES + wv; e < n; e += gridDim.x * EXACT_WAVES) {
-        const u64 ent = A.q.entries[e];
-        const uint32_t pix = (uint32_t)ent;
-        const int d = (int)((ent >> 32) & 0xffff);
-        const unsigned sides = (unsigned)(ent >> 48) & 3u;
-        const int yr = (int)(pix / (uint32_t)W), x = (int)(pix - (uint32_t)yr * (uint32_t)W);
-        const int y = A.row0 + yr, xr = x - d;
-        const double *const cl = A.labL + 3 * ((size_t)y * W + x), *const cr = A.labR + 3 * ((size_t)y * W + xr);
+        const ExactEntry en = exact_decode(A.q.entries[e]);
+        const int yr = (int)(en.pix / (uint32_t)W), x = (int)(en.pix - (uint32_t)yr * (uint32_t)W);
+        const int y = A.row0 + yr, xr = x - en.d;
+        const double *const cl = A.lab[0] + 3 * ((size_t)y * W + x), *const cr = A.lab[1] + 3 * ((size_t)y * W + xr);
         const double cl0 = cl[0], cl1 = cl[1], cl2 = cl[2], cr0 = cr[0], cr1 = cr[1], cr2 = cr[2];
         // tap columns j with both the left column x - p + j and the right column xr - p + j inside the image (xr <= x):
         // `continue` below 0, `break` from the width on (_passive.cpp:65-68); window rows i likewise (:60-62)
@@ -428,20 +429,21 @@ __global__ __launch_bounds__(64 * EXACT_WAVES) void asw_exact_eval_kernel(const 
         const int ilo = max(0, p - y), ihi = min(win, H + p - y);
         const int ntap = (ihi - ilo) * ncol;
         // weight tables (asw_exact_wtab_kernel): w1 of a flagged LEFT pixel, w2 of a flagged RIGHT pixel -- wave-uniform
-        const uint32_t s1 = A.wcap && A.q.flagL && A.q.flagL[pix] ? A.wslotL[pix] : 0xffffffffu;
-        const uint32_t s2 = A.wcap && A.q.flagR && A.q.flagR[pix - (uint32_t)d] ? A.wslotR[pix - (uint32_t)d] : 0xffffffffu;
+        const uint32_t aR = exact_anchor<1>(en);
+        const uint32_t s1 = A.wcap && A.q.flagL && A.q.flagL[en.pix] ? A.wslot[0][en.pix] : 0xffffffffu;
+        const uint32_t s2 = A.wcap && A.q.flagR && A.q.flagR[aR] ? A.wslot[1][aR] : 0xffffffffu;
         const double *const t1 = s1 < A.wcap ? A.wtab + (size_t)s1 * win * win : nullptr;
         const double *const t2 = s2 < A.wcap ? A.wtab + (size_t)s2 * win * win : nullptr;
         double acc = 0.0;                           // lane 0: cost, lane 1: tot
         // entries whose fp32 cost is 0 (EXACT_HINT_ZERO): if every in-image tap has TAD = 0 the reference's cost is exactly 0.0 --
         // `cost += w1*w2*0` for positive weights -- and nothing else has to be computed
         bool all_zero = false;
-        if ((unsigned)(ent >> 48) & EXACT_HINT_ZERO) {
+        if (en.zero) {
             bool nz = false;
             for (int t = lane; t < ntap; t += 64) {
                 const int q = t / ncol, i = ilo + q, j = jlo + (t - q * ncol);
                 const int ii = y - p + i, jj = xr - p + j, kk = x - p + j;
-                nz = nz || __builtin_amdgcn_sad_u8(A.recL[(size_t)ii * W + kk].bgrx, A.recR[(size_t)ii * W + jj].bgrx, 0u) != 0u;
+                nz = nz || __builtin_amdgcn_sad_u8(A.rec[0][(size_t)ii * W + kk].bgrx, A.rec[1][(size_t)ii * W + jj].bgrx, 0u) != 0u;
             }
             all_zero = __builtin_amdgcn_ballot_w64(nz) == 0;
         }
@@ -451,20 +453,9 @@ __global__ __launch_bounds__(64 * EXACT_WAVES) void asw_exact_eval_kernel(const 
                 const int q = (t0 + t) / ncol, i = ilo + q, j = jlo + (t0 + t - q * ncol);
                 const int ii = y - p + i, jj = xr - p + j, kk = x - p + j;
                 const double pr = A.prox[i * win + j];
-                double w1, w2;
-                if (t1) w1 = t1[i * win + j];
-                else {
-                    const double *const tl = A.labL + 3 * ((size_t)ii * W + kk);
-                    const double a0 = tl[0] - cl0, a1 = tl[1] - cl1, a2 = tl[2] - cl2;
-                    w1 = pr * glibc_exp_t(-exact_sqrt(a0 * a0 + a1 * a1 + a2 * a2) / A.gammaC, s_exp);
-                }
-                if (t2) w2 = t2[i * win + j];
-                else {
-                    const double *const tr = A.labR + 3 * ((size_t)ii * W + jj);
-                    const double b0 = tr[0] - cr0, b1 = tr[1] - cr1, b2 = tr[2] - cr2;
-                    w2 = pr * glibc_exp_t(-exact_sqrt(b0 * b0 + b1 * b1 + b2 * b2) / A.gammaC, s_exp);
-                }
-                const int tad = min(40, (int)__builtin_amdgcn_sad_u8(A.recL[(size_t)ii * W + kk].bgrx, A.recR[(size_t)ii * W + jj].bgrx, 0u));
+                const double w1 = t1 ? t1[i * win + j] : exact_weight(A.lab[0], cl0, cl1, cl2, ii, kk, W, pr, A.gammaC, s_exp);
+                const double w2 = t2 ? t2[i * win + j] : exact_weight(A.lab[1], cr0, cr1, cr2, ii, jj, W, pr, A.gammaC, s_exp);
+                const int tad = min(40, (int)__builtin_amdgcn_sad_u8(A.rec[0][(size_t)ii * W + kk].bgrx, A.rec[1][(size_t)ii * W + jj].bgrx, 0u));
                 const double ww = w1 * w2;
                 sw[t] = ww;
                 sc[t] = ww * tad;
@@ -492,8 +483,9 @@ __global__ __launch_bounds__(64 * EXACT_WAVES) void asw_exact_eval_kernel(const 
             const double c = all_zero ? 0.0 : acc / tot;
             A.ecost[e] = c;
             const u64 bits = (u64)__double_as_longlong(c);           // costs are >= 0: the bit patterns order like the values
-            if (sides & EXACT_SIDE_L) atomicMin(A.costL + pix, bits);
-            if (sides & EXACT_SIDE_R) atomicMin(A.costR + (pix - (uint32_t)d), bits);
+            exact_each_side(A, [&](auto side) {
+                if (en.sides & (EXACT_SIDE_L << side)) atomicMin(A.cost[side] + exact_anchor<side>(en), bits);
+            });
         }
     }
 }
@@ -502,15 +494,14 @@ __global__ __launch_bounds__(64 * EXACT_WAVES) void asw_exact_eval_kernel(const 
 __global__ __launch_bounds__(256) void asw_exact_resolve_kernel(const AswExactArgs A)
 {
     if (exact_overflowed(A)) return;
-    const unsigned n = A.q.counter[0];
+    const unsigned n = exact_count(A.q);
     for (unsigned e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += gridDim.x * blockDim.x) {
-        const u64 ent = A.q.entries[e];
-        const uint32_t pix = (uint32_t)ent;
-        const int d = (int)((ent >> 32) & 0xffff);
-        const unsigned sides = (unsigned)(ent >> 48) & 3u;
+        const ExactEntry en = exact_decode(A.q.entries[e]);
         const u64 bits = (u64)__double_as_longlong(A.ecost[e]);
-        if ((sides & EXACT_SIDE_L) && A.costL[pix] == bits) atomicMin(A.idxL + pix, (uint32_t)d);
-        if ((sides & EXACT_SIDE_R) && A.costR[pix - (uint32_t)d] == bits) atomicMin(A.idxR + (pix - (uint32_t)d), pix % (uint32_t)A.W);
+        exact_each_side(A, [&](auto side) {
+            const uint32_t a = exact_anchor<side>(en);
+            if ((en.sides & (EXACT_SIDE_L << side)) && A.cost[side][a] == bits) atomicMin(A.idx[side] + a, exact_windex<side>(en, A.W));
+        });
     }
 }
 
@@ -520,11 +511,11 @@ __global__ __launch_bounds__(256) void asw_exact_patch_kernel(const AswExactArgs
     if (exact_overflowed(A)) return;             // queue overflow (counted; the caller reports it): incomplete candidate sets, the map stays as it is
     const long long n = (long long)A.rows * A.W;
     for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (long long)gridDim.x * blockDim.x) {
-        if (A.q.flagL[q] && A.idxL[q] != 0xffffffffu) {
-            if (A.keyL) A.keyL[q] = (A.keyL[q] & 0xffffffff00000000ull) | (u64)A.idxL[q];
-            else A.disp[q] = (int16_t)A.idxL[q];
-        }
-        if (A.keyR && A.q.flagR[q] && A.idxR[q] != 0xffffffffu) A.keyR[q] = (A.keyR[q] & 0xffffffff00000000ull) | (u64)A.idxR[q];
+        exact_each_side(A, [&](auto side) {
+            if (!(side ? A.q.flagR : A.q.flagL)[q] || A.idx[side][q] == 0xffffffffu) return;
+            if (A.keys[side]) A.keys[side][q] = (A.keys[side][q] & 0xffffffff00000000ull) | (u64)A.idx[side][q];
+            else A.disp[q] = (int16_t)A.idx[side][q];
+        });
     }
 }
 

@@ -150,6 +150,8 @@ __device__ __forceinline__ void asw_taps(float (&accN)[RX][ASW_RD], float (&accS
 // cost itself.  cost <= 20: bits(cost); cost > 20: 0xC0000000 - bits(40 - cost), which
 // is > bits(20.0f) and decreasing in (40 - cost): a monotone map of the cost that keeps
 // the resolution of the accurate operand.
+// The image of a cost above 20, from inv = 40 - cost (also on the host: the thresholds of the exact mode are such images)
+__host__ __device__ __forceinline__ uint32_t asw_inv_key(const float inv) { return 0xC0000000u - __builtin_bit_cast(uint32_t, inv); }
 __device__ __forceinline__ uint32_t asw_cost_key(const float n, const float s, float &cost)
 {
     const float t40 = n + s;
@@ -159,7 +161,7 @@ __device__ __forceinline__ uint32_t asw_cost_key(const float n, const float s, f
     }
     const float inv = ASW_TAD_CAP * s / t40;
     cost = ASW_TAD_CAP - inv;
-    return 0xC0000000u - __float_as_uint(inv);
+    return asw_inv_key(inv);
 }
 
 // ---- exact mode: near-tie selection (called from asw_epilogue.inc, the one epilogue of the four kernel families) ----------
@@ -213,10 +215,28 @@ __device__ __forceinline__ bool exact_near_local(uint32_t key, uint32_t kb, uint
     return kb >= EXACT_KEY_HIGH && __uint_as_float(0xC0000000u - key) >= 20.0f - 20.0f * 1.1920929e-7f * (float)tol;
 }
 
-__device__ __forceinline__ u64 exact_entry(uint32_t pix, int d, unsigned sides)
+// The one codec of a queue entry (AswExactQueue::entries): `sides` = EXACT_SIDE_* | EXACT_HINT_ZERO.  Host code uses it too.
+__host__ __device__ __forceinline__ u64 exact_entry(uint32_t pix, int d, unsigned sides)
 {
     return (u64)pix | ((u64)(uint32_t)d << 32) | ((u64)sides << 48);
 }
+struct ExactEntry { uint32_t pix; int d; unsigned sides; bool zero; };      // sides: EXACT_SIDE_L | EXACT_SIDE_R (0: cost only); zero: EXACT_HINT_ZERO
+__host__ __device__ __forceinline__ ExactEntry exact_decode(u64 ent)
+{
+    return {(uint32_t)ent, (int)((ent >> 32) & 0xffff), (unsigned)(ent >> 48) & (EXACT_SIDE_L | EXACT_SIDE_R), ((ent >> 48) & EXACT_HINT_ZERO) != 0};
+}
+
+// Slots of the pass's counter block (the first 64 bytes of the flag buffer, zeroed before every call).  The final queue's
+// AswExactQueue::counter points at EXACT_CTR_ENTRIES, the raw queue's at EXACT_CTR_RAW.
+enum ExactCounter : unsigned {
+    EXACT_CTR_ENTRIES = 0,       // entries appended to the final queue (may exceed its cap)
+    EXACT_CTR_FLAGGED_L = 1,     // flagged left pixels
+    EXACT_CTR_FLAGGED_R = 2,     // flagged right pixels
+    EXACT_CTR_RAW = 4,           // entries appended to the raw queue of a merging call (may exceed its cap)
+    EXACT_CTR_WSLOTS = 6,        // weight-table slots asked for (may exceed AswExactArgs::wcap)
+    EXACT_CTR_COUNT = 16         // dwords in the block
+};
+__device__ __forceinline__ unsigned exact_count(const AswExactQueue &q) { return q.counter[0]; }      // entries appended to THIS queue
 
 // Append (pix, d, sides) for the lanes that `want` it.  Wave-aggregated: ONE atomicAdd on the queue counter per wave and call
 // (a flat or saturated frame makes every candidate a near-tie: per-lane atomics on one address would serialise the whole grid).

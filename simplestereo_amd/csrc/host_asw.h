@@ -165,6 +165,9 @@ struct AswRun : AswCall {
     AswWaveGeom wave;                 // strip of the wave kernel, filled by asw_prepare_volume
     AswExactQueue xq_final{}, xq_raw{}, xq_kernel{};      // exact mode: the final near-tie queue, for merging calls the raw one, and the one the kernels append to
 };
+// exact mode, before and after the aggregation (host_asw_exact.h, the section behind this one: it works on the AswRun)
+int asw_exact_prepare(AswRun &r, bool direct);
+int asw_exact_pass(AswRun &r, bool direct);
 
 // One disparity chunk and no right-referenced pass: each pixel is decided by exactly one workgroup, which then
 // writes the disparity itself -- no key buffer, atomics or decode kernel (34 instead of 48+ bytes of HBM per pixel).
@@ -598,15 +601,13 @@ int asw_device_impl(Ctx &c, const AswCall &q)
                 if (r.need_keys && (rc = reset_keys(c.keyL, r.nout, s))) return rc;
                 if (q.consistent && (rc = reset_keys(c.keyR, r.nout, s))) return rc;
             }
-            if ((rc = asw_exact_prepare(c, q.W, q.rows, q.win, r.nD, q.gammaC, q.consistent, asw_is_direct(r, final_geom), s, r.xq_final, r.xq_raw, r.xq_kernel))) return rc;
+            if ((rc = asw_exact_prepare(r, asw_is_direct(r, final_geom)))) return rc;
         }
         Timed agg(c, s, SSAMD_K_ASW_AGG);
         if ((rc = asw_launch(r, final_geom))) return rc;
     }
     const bool direct = asw_is_direct(r, r.geom);
-    if (r.exact && r.nD >= 1 &&
-        (rc = asw_exact_pass(c, r.xq_final, r.xq_raw, q.H, q.W, q.row0, q.rows, q.win, q.maxD, q.minD, q.gammaC, q.gammaP, q.consistent, direct, q.d_disp, s)))
-        return rc;
+    if (r.exact && r.nD >= 1 && (rc = asw_exact_pass(r, direct))) return rc;
     if (!direct && q.skip > 0) {
         // decode / left-right check of the two bands only; the rows between keep what the interior call wrote
         if ((rc = launch_finalize(c, SSAMD_K_ASW_FIN, q.consistent, 0, q.skip_at, q.W, q.d_disp, s)) ||

@@ -154,7 +154,7 @@ struct Ctx {
     int32_t *ftpBandHost = nullptr;     // pinned staging of the bands: the asynchronous upload reads it after the call returned
     size_t ftpBandHostCap = 0;          // ... in int32 pairs
     hipEvent_t ftp_band_copied = nullptr;   // recorded behind that upload; the next call waits for it before it refills the staging
-    unsigned int xcap = 0, xrawcap = 0; // queue capacities of the last exact call
+    AswExactQueue xq[2] = {};           // the final and the raw queue (entries == nullptr: none) of the last exact call
     TableCache proxTabs{8}, gswTabs{4}, proxTabs64{8};
     std::map<const void *, int> max_dyn_lds;   // hipFuncAttributeMaxDynamicSharedMemorySize already granted per kernel
     hipEvent_t scratch_free = nullptr;  // recorded after the last kernel that uses the scratch buffers

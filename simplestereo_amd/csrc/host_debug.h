@@ -42,6 +42,7 @@ int ssamd_debug_exact_costs(const uint8_t *img1, const uint8_t *img2, int height
         (rc = c->recR.reserve(npix * sizeof(PixRec))) || (rc = c->xlabL.reserve(npix * 24)) || (rc = c->xlabR.reserve(npix * 24)) ||
         (rc = c->xqueue.reserve((size_t)std::max(n, 1) * 8)) || (rc = c->xcost.reserve((size_t)std::max(n, 1) * 8)) || (rc = c->xctr.reserve(64)))
         return rc;
+    if (c->xq[0].entries) c->xq[0].entries = (u64 *)c->xqueue.ptr;      // (the reservation may have moved the last exact call's queue buffer)
     HIP_TRY(hipMemcpyAsync(c->imgL.ptr, img1, npix * 3, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(c->imgR.ptr, img2, npix * 3, hipMemcpyHostToDevice, s));
     const int blocks = (int)std::min<long long>((2 * (long long)npix + 255) / 256, 256 * 8);
@@ -53,16 +54,17 @@ int ssamd_debug_exact_costs(const uint8_t *img1, const uint8_t *img2, int height
     for (int k = 0; k < n; ++k) {
         const int y = yxd[3 * k], x = yxd[3 * k + 1], d = yxd[3 * k + 2];
         if (y < 0 || y >= height || x < 0 || x >= width || d < 0 || x - d < 0) return fail(SSAMD_EINVAL, "candidate %d outside the image", k);
-        ent[k] = (u64)((uint32_t)y * (uint32_t)width + (uint32_t)x) | ((u64)(uint32_t)d << 32);       // sides = 0: cost only
+        ent[k] = exact_entry((uint32_t)y * (uint32_t)width + (uint32_t)x, d, 0u);       // sides = 0: cost only
     }
-    const unsigned int ctr[16] = {(unsigned int)n};            // (counter[7] = the eval kernel's work counter)
+    unsigned int ctr[EXACT_CTR_COUNT] = {};
+    ctr[EXACT_CTR_ENTRIES] = (unsigned int)n;
     HIP_TRY(hipMemcpyAsync(c->xqueue.ptr, ent.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(c->xctr.ptr, ctr, sizeof(ctr), hipMemcpyHostToDevice, s));
     const double *d_prox = nullptr;
     if ((rc = get_prox64(*c, winSize, gammaP, s, &d_prox))) return rc;
     AswExactArgs x{};
-    x.recL = (const PixRec *)c->recL.ptr; x.recR = (const PixRec *)c->recR.ptr;
-    x.labL = (const double *)c->xlabL.ptr; x.labR = (const double *)c->xlabR.ptr;
+    x.rec[0] = (const PixRec *)c->recL.ptr; x.rec[1] = (const PixRec *)c->recR.ptr;
+    x.lab[0] = (const double *)c->xlabL.ptr; x.lab[1] = (const double *)c->xlabR.ptr;
     x.prox = d_prox; x.q.entries = (u64 *)c->xqueue.ptr; x.q.counter = (unsigned int *)c->xctr.ptr; x.q.cap = (unsigned int)std::max(n, 1);
     x.ecost = (double *)c->xcost.ptr;
     x.H = height; x.W = width; x.win = winSize; x.pad = winSize / 2; x.row0 = 0; x.rows = height; x.gammaC = gammaC;
@@ -84,16 +86,16 @@ int ssamd_debug_exact_queue(int which, long long max_n, unsigned long long *entr
     int rc = get_ctx(-1, c);
     if (rc) return rc;
     *n = 0;
-    unsigned int ctr[5];
+    unsigned int ctr[EXACT_CTR_COUNT];
     if ((rc = asw_exact_counters(*c, ctr))) return rc;      // (all zero when no exact call has run: nothing to copy)
-    const unsigned int cnt = which ? ctr[4] : ctr[0], cap = which ? c->xrawcap : c->xcap;
+    const unsigned int cnt = ctr[which ? EXACT_CTR_RAW : EXACT_CTR_ENTRIES], cap = c->xq[which ? 1 : 0].cap;
     *n = cnt;
     const size_t m = (size_t)std::min<long long>(std::min<unsigned int>(cnt, cap), max_n);
     if (m == 0) return SSAMD_OK;
-    const void *src = which ? c->xraw.ptr : c->xqueue.ptr;
-    if (!src) return SSAMD_OK;
-    HIP_TRY(hipMemcpy(entries, src, m * 8, hipMemcpyDeviceToHost));
-    if (which && keys) HIP_TRY(hipMemcpy(keys, (const char *)src + (size_t)c->xrawcap * 8, m * 4, hipMemcpyDeviceToHost));
+    const AswExactQueue &q = c->xq[which ? 1 : 0];         // (as asw_exact_prepare carved it)
+    if (!q.entries) return SSAMD_OK;
+    HIP_TRY(hipMemcpy(entries, q.entries, m * 8, hipMemcpyDeviceToHost));
+    if (which && keys) HIP_TRY(hipMemcpy(keys, q.ekeys, m * 4, hipMemcpyDeviceToHost));
     return SSAMD_OK;
 }
 

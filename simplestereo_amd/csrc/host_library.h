@@ -74,10 +74,11 @@ int ssamd_counter(int device, const char *name, long long *value)
     }
     else if (n == "exact_entries" || n == "exact_flagged_left" || n == "exact_flagged_right" || n == "exact_overflow" || n == "exact_raw_entries") {
         // of the LAST exact call on this device: candidates re-evaluated in fp64, pixels with near-ties, whether the queue overflowed
-        unsigned int ctr[5];
+        unsigned int ctr[EXACT_CTR_COUNT];
         if ((rc = asw_exact_counters(*c, ctr))) return rc;
-        *value = n == "exact_entries" ? ctr[0] : n == "exact_flagged_left" ? ctr[1] : n == "exact_flagged_right" ? ctr[2] :
-                 n == "exact_raw_entries" ? ctr[4] : ((ctr[0] > c->xcap || (c->xrawcap && ctr[4] > c->xrawcap)) ? 1 : 0);
+        *value = n == "exact_entries" ? ctr[EXACT_CTR_ENTRIES] : n == "exact_flagged_left" ? ctr[EXACT_CTR_FLAGGED_L] :
+                 n == "exact_flagged_right" ? ctr[EXACT_CTR_FLAGGED_R] : n == "exact_raw_entries" ? ctr[EXACT_CTR_RAW] :
+                 ((ctr[EXACT_CTR_ENTRIES] > c->xq[0].cap || (c->xq[1].cap && ctr[EXACT_CTR_RAW] > c->xq[1].cap)) ? 1 : 0);
     }
     else return fail(SSAMD_EINVAL, "unknown counter %s", name);
     return SSAMD_OK;

@@ -57,8 +57,8 @@ using namespace ssamd;
 // ---- the host side, section by section (each opens at most one anonymous namespace and one extern "C" block)
 #include "host_context.h"       // last error, option snapshot (ssamd_options.h) and the planners' headers, DevBuf, profiler, Ctx / get_ctx, ScratchOrder, the host-buffer route
 #include "host_geometry.h"      // per-shape geometry caches around the planners, the autotuner's rounds
-#include "host_asw_exact.h"     // ASW: the fp64 tie-break pass before and after the aggregation, its counters
 #include "host_asw.h"           // ASW: tables, kernel variants, AswCall / AswRun and the steps of one call, alternate rows
+#include "host_asw_exact.h"     // ASW: the fp64 tie-break pass before and after the aggregation (on the AswRun), its scratch layout, its counters
 #include "host_gsw.h"           // GSW: weight table, GswCall, one call
 #include "host_matchers.h"      // matcher ABI: HostJob / host_rows / run_strips, every ssamd_asw* and ssamd_gsw* entry point
 #include "host_rig.h"           // remap and reproject

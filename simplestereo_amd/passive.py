@@ -278,7 +278,8 @@ class StereoASW(_Matcher):
         reference's own expression and summation order (reference ``_passive.cpp:37-50, 57-88``) and those argmins are redone
         -- the map is then the reference's wherever double precision can tell the candidates apart: bit for bit on every golden
         map, the whole bench frames and 38 642 random frames (``ssamd_asw_exact*``, include/ssamd.h).  Costs about
-        1 % at 1080p / 193 disparities and O(H * W) scratch.  ``False``: the fp32 argmin only (>= 99.99 % of the pixels identical on
+        1 % at 1080p / 193 disparities and O(H * W) scratch (about 150 bytes per pixel plus 64 MiB of weight tables at 1080p,
+        48 bytes per pixel more with ``consistent``: 0.4 - 0.5 GB; include/ssamd.h).  ``False``: the fp32 argmin only (>= 99.99 % of the pixels identical on
         full frames, ~99.9 % on a class-default photograph).  ``True`` with ``alternate=True`` raises.  If the candidate queue
         overflows (a frame of saturated noise), the fp32 map is returned and a ``RuntimeWarning`` is issued on host-array calls
         (``_native.counter("exact_overflow")`` for device tensors).
