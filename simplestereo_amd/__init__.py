@@ -12,11 +12,11 @@ The matchers run as hand-written HIP kernels (gfx950) behind the C ABI of
 ``libssamd.so`` (see ``include/ssamd.h``); nothing here falls back to the CPU.
 """
 from . import passive
-from ._rigs import StereoRig, RectifiedStereoRig
+from ._rigs import StereoRig, RectifiedStereoRig, StructuredLightRig
 from . import strips
 from . import points
 from . import unwrapping
 from . import active
 
 __version__ = "0.6.0"
-__all__ = ["passive", "StereoRig", "RectifiedStereoRig", "strips", "points", "unwrapping", "active"]
+__all__ = ["passive", "StereoRig", "RectifiedStereoRig", "StructuredLightRig", "strips", "points", "unwrapping", "active"]

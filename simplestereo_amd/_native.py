@@ -1,5 +1,5 @@
-"""ctypes binding of libssamd.so (C ABI in include/ssamd.h, include/ssamd_active.h, include/ssamd_graycode.h and
-include/ssamd_ftp_mapping.h).
+"""ctypes binding of libssamd.so (C ABI in include/ssamd.h, include/ssamd_active.h, include/ssamd_graycode.h,
+include/ssamd_ftp_mapping.h and include/ssamd_structured_light.h).
 
 This is the only place Python touches the native library.  There is no Python or
 CPU fallback for the operators: if the library is missing, or no HIP device is
@@ -24,6 +24,7 @@ ABI_VERSION = 8
 ACTIVE_VERSION = 1         # SSAMD_ACTIVE_VERSION of include/ssamd_active.h, the second public header of the same library
 GRAYCODE_VERSION = 1       # SSAMD_GRAYCODE_VERSION of include/ssamd_graycode.h, the third
 FTP_MAPPING_VERSION = 1    # SSAMD_FTP_MAPPING_VERSION of include/ssamd_ftp_mapping.h, the fourth
+SL_VERSION = 1             # SSAMD_SL_VERSION of include/ssamd_structured_light.h, the fifth
 GRAYCODE_BLOCK = 1024      # SSAMD_GRAYCODE_BLOCK: pixels per block of the decode counts and the offsets
 
 (K_LAB, K_ASW_AGG, K_ASW_FIN, K_GSW_AGG, K_GSW_FIN, K_REMAP, K_REPROJECT, K_ASW_ALT, K_ASW_EXACT, K_UNWRAP, K_FTP,
@@ -84,6 +85,9 @@ _SIGNATURES = (
     # include/ssamd_ftp_mapping.h (SSAMD_FTP_MAPPING_VERSION); tests/test_ftp_mapping_cpu.py holds these rows to that header
     ("piiippidp", "ssamd_ftp_carrier_phase"),
     ("piiiiDDddp", "ssamd_ftp_mapping_cloud"),
+    # include/ssamd_structured_light.h (SSAMD_SL_VERSION); tests/test_phaseshift_cpu.py holds these rows to that header
+    ("piiipp" + 6 * "i" + "DDiiip", "ssamd_phaseshift_decode"),
+    ("ppliiiDp", "ssamd_sl_triangulate"),
 ) for last, suffix in (("i", ""), ("p", "_device")))
 _RETURN_STRING = ("ssamd_last_error", "ssamd_kernel_name")
 _CTYPES = {"i": ctypes.c_int, "l": ctypes.c_longlong, "d": ctypes.c_double, "f": ctypes.c_float, "p": ctypes.c_void_p,

@@ -3,7 +3,7 @@ _rigs
 =====
 Stereo rig parameter containers with the API of ``simplestereo.StereoRig`` /
 ``simplestereo.RectifiedStereoRig`` (reference ``simplestereo/_rigs.py:22-338``,
-``341-628``) -- the plumbing that feeds rectified pairs to ``passive.StereoASW``
+``341-628``) and ``simplestereo.StructuredLightRig`` (``631-715``) -- the plumbing that feeds rectified pairs to ``passive.StereoASW``
 (``examples/009 StereoMatchingASW.py:20-39``).
 
 Own code, numpy only: OpenCV is not a dependency (it is absent on the MI355X
@@ -17,6 +17,9 @@ cv2.undistortPoints (4 corners)        :func:`_undistort_points`
 cv2.initUndistortRectifyMap            :func:`_init_undistort_rectify_map`
 cv2.remap (constant border)            :func:`_remap`
 cv2.reprojectImageTo3D                 :meth:`RectifiedStereoRig.get3DPoints`
+cv2.perspectiveTransform,              :meth:`StructuredLightRig.triangulate`
+cv2.undistortPoints (every point)      (``sl_triangulate_kernel``)
+cv2.undistort                          :meth:`StructuredLightRig.undistortCameraImage`
 ====================================  ==========================================
 
 Parity status: JSON round trip and the 3x3 algebra are pinned by the reference's
@@ -31,7 +34,7 @@ import numpy as np
 from . import _native
 from ._native import is_device_tensor as _is_device_tensor
 
-__all__ = ["StereoRig", "RectifiedStereoRig"]
+__all__ = ["StereoRig", "RectifiedStereoRig", "StructuredLightRig"]
 
 # OpenCV interpolation flag values, so callers can pass cv2.INTER_* or these
 INTER_NEAREST = 0
@@ -569,3 +572,130 @@ class RectifiedStereoRig(StereoRig):
         _native.call_on_stream(d, _native.lib().ssamd_reproject_device, d.data_ptr(), h, w,
                                Q.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), out.data_ptr())
         return out
+
+
+class StructuredLightRig(StereoRig):
+    """
+    A camera-projector rig with the structured-light methods of ``simplestereo.StructuredLightRig`` (reference
+    ``_rigs.py:631-715``): camera in position 1 (world origin), projector in position 2.
+
+    Parameters
+    ----------
+    r : StereoRig
+        The calibrated rig to extend; anything else is ``ValueError("Invalid argument!")``.
+
+    The attributes are the reference's: ``R1`` and ``R2``, the rectifying transforms of ``rectification._lowLevelRectify``
+    (no new intrinsics), ``R_inv`` (4 x 4, the inverse of the common orientation, padded) -- and ``R``, which the reference
+    overwrites with the common orientation once the transforms are built.  ``getBaseline()`` reads ``R``, so it differs from
+    the plain rig's in the last bits; that baseline is the one :meth:`triangulate` uses, as in the reference.
+    """
+
+    def __init__(self, r):
+        if not isinstance(r, StereoRig):
+            raise ValueError("Invalid argument!")
+        super().__init__(r.res1, r.res2, r.intrinsic1, r.intrinsic2, r.distCoeffs1, r.distCoeffs2, r.R, r.T, r.F, r.E,
+                         r.reprojectionError)
+        self._computeMatrices()
+
+    def _computeMatrices(self):
+        from .active import _low_level_rectify, _r_inv4
+        self.R1, self.R2, self.R = _low_level_rectify(self)
+        self.R_inv = _r_inv4(self.R)
+        self._cache = {}                          # active._cached_maps' entries: the camera's undistortion maps, per device
+
+    @classmethod
+    def fromFile(cls, filepath):
+        """A StructuredLightRig from the JSON file of a :class:`StereoRig`."""
+        return cls(StereoRig.fromFile(filepath))
+
+    def _geometry(self):
+        """The ``SSAMD_FTP_CLOUD_NGEOM`` doubles of ``ssamd_sl_triangulate``: K2, ``distCoeffs2``, ``R1``, ``R2``, the inverse common
+        orientation and ``getBaseline()`` (computed with the overwritten ``R``)."""
+        from .active import _triangulation_geom
+        dist = _dist_vector(self.distCoeffs2)                      # NotImplementedError for a tilted sensor
+        g = _triangulation_geom(self, dist, self.R1, self.R2, self.R_inv[:3, :3])
+        if not np.isfinite(g).all():
+            raise ValueError("the rig gives a geometry that is not finite")
+        return g
+
+    @staticmethod
+    def _points(p, name):
+        """-> float64 [n, 2], contiguous, where it is (host array or device tensor)"""
+        if _is_device_tensor(p):
+            import torch
+            if p.dtype == torch.bool or p.is_complex():
+                raise TypeError("%s must be of a real dtype" % name)
+            if p.dim() < 1 or p.shape[-1] != 2:
+                raise ValueError("%s: the last dimension must be 2" % name)
+            return p.reshape(-1, 2).to(torch.float64).contiguous()
+        if not isinstance(p, np.ndarray):
+            raise TypeError("%s must be an ndarray or a CUDA/HIP tensor" % name)
+        if p.dtype.kind not in "iuf":
+            raise TypeError("%s must be of a real dtype" % name)
+        if p.ndim < 1 or p.shape[-1] != 2:
+            raise ValueError("%s: the last dimension must be 2" % name)
+        return np.ascontiguousarray(p.reshape(-1, 2), dtype=np.float64)
+
+    def triangulate(self, camPoints, projPoints):
+        """
+        Triangulate camera-projector correspondences (reference ``_rigs.py:654-700``), by one HIP kernel
+        (``sl_triangulate_kernel``): ``R1`` on the camera points, ``cv2.undistortPoints(projPoints, K2, distCoeffs2, P=K2)``
+        (five iterations), ``R2``, ``getBaseline() / |disparity|`` and the common rotation undone -- the operations that end
+        ``active.ftpCloud`` and ``active.GrayCode.getCloud``, by the same device function, fp64.
+
+        Parameters
+        ----------
+        camPoints, projPoints : numpy.ndarray or CUDA/HIP tensor
+            Ordered corresponding (x, y) couples of the camera and of the projector, of any real dtype; the last dimension
+            must be 2.  Camera points must already be undistorted.  Both on the host or both on one device.  They are
+            converted to float64: float32 input gives float64 results (the reference's have float32 precision then).
+
+        Returns
+        -------
+        numpy.ndarray or tensor
+            float64 ``(n, 1, 3)``; three NaN where a projector point holds a NaN.  A tensor on the inputs' device, computed on
+            its current stream, for tensors.
+        """
+        import ctypes
+        pc, pp = self._points(camPoints, "camPoints"), self._points(projPoints, "projPoints")
+        if _is_device_tensor(pc) != _is_device_tensor(pp) or (_is_device_tensor(pc) and pc.device != pp.device):
+            raise TypeError("camPoints and projPoints must both be on the host or both on one device")
+        if pc.shape[0] != pp.shape[0]:
+            raise ValueError("%d camera points but %d projector points" % (pc.shape[0], pp.shape[0]))
+        n = int(pc.shape[0])
+        gp = self._geometry().ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        return _native.run("ssamd_sl_triangulate", (pc, pp), (n, 1, 3), lambda c, p, out: (c, p, n, 1, 0, 0, gp, out),
+                           (_native.EINVAL, _native.ELIMIT))
+
+    def undistortCameraImage(self, imgObj):
+        """
+        Undistort a camera image: ``cv2.undistort(imgObj, intrinsic1, distCoeffs1)`` (reference ``_rigs.py:702-715``), as
+        ``active.StereoFTP`` undistorts its frames -- the float32 maps of ``initUndistortRectifyMap(K1, D1, I, K1, res1)`` and a
+        bilinear remap with a constant border 0.
+
+        Parameters
+        ----------
+        imgObj : numpy.ndarray or CUDA/HIP tensor
+            uint8 ``[H, W]`` or ``[H, W, 3]``.  A host array goes through :func:`_remap`, a device tensor through
+            ``remap_bgr_kernel`` (a gray tensor as three equal channels, of which the first is returned: the bilinear
+            arithmetic is per channel, so the bytes are the same).
+
+        Returns
+        -------
+        The undistorted image, of the rig's ``res1``, where the input is.
+        """
+        from .active import _cached_maps
+        if not _is_device_tensor(imgObj):
+            mx, my = _cached_maps(self._cache, self)
+            return _remap(imgObj, mx, my, INTER_LINEAR)
+        import torch
+        if imgObj.dtype != torch.uint8 or imgObj.dim() not in (2, 3) or (imgObj.dim() == 3 and imgObj.shape[2] != 3):
+            raise ValueError("device undistortion expects a uint8 [H,W] or [H,W,3] tensor")
+        gray = imgObj.dim() == 2
+        src = (imgObj.unsqueeze(2).expand(-1, -1, 3) if gray else imgObj).contiguous()
+        dmx, dmy = _cached_maps(self._cache, self, imgObj.device)
+        h, w = int(dmx.shape[0]), int(dmx.shape[1])
+        out = torch.empty((h, w, 3), dtype=torch.uint8, device=imgObj.device)
+        _native.call_on_stream(src, _native.lib().ssamd_remap_bgr_device, src.data_ptr(), int(src.shape[0]), int(src.shape[1]),
+                               dmx.data_ptr(), dmy.data_ptr(), h, w, INTER_LINEAR, out.data_ptr())
+        return out[:, :, 0].contiguous() if gray else out

@@ -6,7 +6,8 @@ frame in, point cloud out, and the steps it is made of -- the central stripe, th
 and the triangulation of the unwrapped phase -- each per-pixel step executed by one HIP kernel on an AMD MI355X through the C
 ABI of ``libssamd.so`` (``ssamd_ftp_phase``, ``ssamd_ftp_cloud``: ``include/ssamd.h``; ``ssamd_ftp_reference``,
 ``ssamd_stripe_centroids``: ``include/ssamd_active.h``; ``ssamd_ftp_carrier_phase``, ``ssamd_ftp_mapping_cloud``:
-``include/ssamd_ftp_mapping.h``) -- and Gray-code structured light, ``GrayCode``.  No cv2 call anywhere.
+``include/ssamd_ftp_mapping.h``) -- and two more structured-light methods, Gray code (``GrayCode``) and phase shifting with
+heterodyne unwrapping (``PhaseShift``).  No cv2 call anywhere.
 
     import simplestereo_amd as ss
     ftp = ss.active.StereoFTP(rig, ss.active.buildFringe(period, stripeColor="r"), period)
@@ -27,6 +28,11 @@ ABI of ``libssamd.so`` (``ssamd_ftp_phase``, ``ssamd_ftp_cloud``: ``include/ssam
 
     points = ss.active.GrayCode(rig).getCloud(images)                   # float64 (n, 1, 3); images uint8 [N, H, W] or paths
     proj = ss.active.grayCodeDecode(images, rig.res2, white_thr=5)      # int32 [H, W, 2]: (xDec, yDec) or (-1, -1)
+
+    patterns = ss.active.phaseShiftPattern(periods, rig.res2)           # uint8 [4 (nx + ny), Hp, Wp]
+    cloud = ss.active.PhaseShift(rig, periods).getCloud(images)         # float64 [H, W, 3], NaN where masked
+    proj = ss.active.phaseShiftDecode(images, periods, rig.res2)        # float64 [H, W, 2]: (px, py)
+    points = ss.StructuredLightRig(rig).triangulate(camPoints, proj)    # float64 (n, 1, 3): any correspondences
 
 ``ftpPhase`` is the demodulation of ``StereoFTP.getCloud`` (``active.py:675-737``; the same lines are
 ``StereoFTP_PhaseOnly.getPhase``, ``:2012-2074``): gray by the channel maximum, a row-wise FFT of the object image and of
@@ -74,6 +80,15 @@ parity with cv2 itself is pinned only where ``cv2.structured_light`` is installe
 ``GrayCodeDouble`` stays out: the reference's version cannot run (it indexes a projector-shaped array with camera coordinates,
 adds 0.5 to an integer array in place and uses a ``self.R_inv`` it never defines); ``grayCodeDecode`` of the two cameras' stacks
 is the piece to write one's own from.
+
+``PhaseShift`` is phase shifting with heterodyne unwrapping [Reich 1997], the third decoding method of the reference, which
+writes it out in ``calibration.phaseShift`` (``calibration.py:656-687`` and ``:726-738``; C ABI in
+``include/ssamd_structured_light.h``) and uses it on chessboard corners only.  ``phaseShiftDecode`` runs those three closures --
+the four-step wrapped phase, the period-to-period ``unwrap``, ``getProjCoord`` -- on every camera pixel
+(``phaseshift_decode_kernel``: a dense correspondence map), ``phaseShiftPattern`` makes the images with ``buildFringe``, and
+``PhaseShift.getCloud`` ends with ``StructuredLightRig.triangulate`` (``sl_triangulate_kernel``: the reference's general entry
+point for correspondences of any origin, by the device function ``ftpCloud`` ends with) on the pixel grid.  Camera pixels and
+projector coordinates carry no half-pixel offsets there, the convention of that calibration routine.
 
 The band is the reference's, decided exactly (numpy's mask on ``np.fft.fftfreq``); the phase is not bit-identical to
 numpy's pocketfft -- the kernel sums a band-limited direct DFT in another order -- but agrees with the exact angle to a few
@@ -177,6 +192,24 @@ non-empty region reaching outside the image
 PIL absent: ``generateGrayCodeImgs``, a list of paths      ``ImportError``
 =========================================================  =======================
 
+``phaseShiftPattern``, ``phaseShiftDecode``, ``PhaseShift`` and ``PhaseShift.getCloud`` (images, maps and the resolution as in the
+table above):
+
+=========================================================  =======================
+condition                                                  exception
+=========================================================  =======================
+``periods`` not a pair of sequences of 1 .. 8              ``ValueError``
+(``MAX_PERIODS``) finite positive numbers
+fewer images than ``4 * (nx + ny)``                        ``ValueError``
+``min_modulation`` neither ``None`` nor a number >= 0      ``ValueError``
+``roi`` not four non-negative integers (x, y, width,       ``ValueError``
+height) inside the image
+``rig`` not a ``StereoRig``                                ``ValueError("Invalid argument!")``
+``getCloud``: an image that is not of ``res1``             ``ValueError("Image size of {index} is mismatch!")``
+``getCloud``: a rig whose geometry is not finite           ``ValueError``
+``distCoeffs2`` with a tilted sensor (tauX, tauY)          ``NotImplementedError``
+=========================================================  =======================
+
 All of them are raised before any native call.  An image or a phase map with no rows or no columns gives an empty array;
 ``findCentralStripe`` of such an image is ``None``; an empty ``roi`` gives ``(0, 1, 3)`` points.
 """
@@ -188,13 +221,14 @@ import os
 import numpy as np
 
 from . import _native
-from ._rigs import INTER_LINEAR, _dist_vector, _distort, _init_undistort_rectify_map, _remap, _undistort_points
+from ._rigs import INTER_LINEAR, StructuredLightRig, _dist_vector, _distort, _init_undistort_rectify_map, _remap, _undistort_points
 from ._native import c_double as _c_double, is_device_tensor as _is_device_tensor
 
 __all__ = ["ftpPhase", "ftpCloud", "ftpFringeOrder", "ftpGeometry", "FtpGeometry", "MAX_WIDTH", "ftpReference",
            "findCentralStripe", "buildFringe", "StereoFTP", "grayCodePattern", "generateGrayCodeImgs", "grayCodeDecode", "GrayCode",
            "GrayCodeSingle", "MAX_PROJECTOR", "ftpCarrierPhase", "ftpStripePhase", "ftpMappingCloud", "ftpMappingGeometry",
-           "FtpMappingGeometry", "StereoFTP_Mapping", "StereoFTP_PhaseOnly"]
+           "FtpMappingGeometry", "StereoFTP_Mapping", "StereoFTP_PhaseOnly", "phaseShiftPattern", "phaseShiftDecode", "PhaseShift",
+           "MAX_PERIODS"]
 
 MAX_WIDTH = 8192          # SSAMD_FTP_MAX_W: twiddle table, gray rows and a chunk of bins of one row in 160 KiB of LDS
 MAX_PROJECTOR = 65536     # Gray code: at most 16 bits per projector axis, 64 pattern images
@@ -1622,3 +1656,213 @@ class GrayCode:
 
 
 GrayCodeSingle = GrayCode
+
+
+# ------------------------------------------------------------------------------------------------ phase shifting
+MAX_PERIODS = 8           # SSAMD_SL_MAX_PERIODS: periods per projector axis
+_MOD_THR2_ALL = 2 * 255 * 255 + 1      # above every a^2 + b^2 of 8-bit images: masks all
+
+
+def _periods(periods):
+    """-> (float64 [nx], float64 [ny]) of ``periods = (list_x, list_y)``"""
+    try:
+        lists = tuple(periods)
+    except TypeError:
+        lists = ()
+    if len(lists) != 2:
+        raise ValueError("periods must be (list_x, list_y)")
+    out = []
+    for axis, name in zip(lists, "xy"):
+        try:
+            vals = [_finite(v, "a period") for v in axis]
+        except TypeError:
+            raise ValueError("periods must be (list_x, list_y)") from None
+        if not 1 <= len(vals) <= MAX_PERIODS:
+            raise ValueError("%d %s-periods: must be 1 .. %d" % (len(vals), name, MAX_PERIODS))
+        if min(vals) <= 0:
+            raise ValueError("periods must be positive")
+        out.append(np.array(vals, dtype=np.float64))
+    return out[0], out[1]
+
+
+def _mod_thr2(min_modulation):
+    """``sqrt(a^2 + b^2) / 2 < m`` on integers ``a``, ``b`` is ``a^2 + b^2 < ceil(4 m^2)``"""
+    if min_modulation is None:
+        return 0
+    m = _number(min_modulation, "min_modulation")
+    if not m >= 0:
+        raise ValueError("min_modulation must be a number >= 0 or None")
+    return int(min(math.ceil(min(4.0 * m * m, float(_MOD_THR2_ALL))), _MOD_THR2_ALL))
+
+
+def phaseShiftPattern(periods, projRes):
+    """
+    The four-step phase-shift images of a projector, in the order :func:`phaseShiftDecode` reads them (the image-set order of
+    the reference's ``calibration.phaseShift``): for each x-period ``T`` the four gray fringes
+    ``buildFringe(T, shift=i * T / 4, dims=projRes)``, ``i = 0 .. 3`` -- ``cos(theta + i pi / 2)`` --, then for each y-period
+    the same with ``vertical=True``.
+
+    Parameters
+    ----------
+    periods : (list_x, list_y)
+        Fringe periods in projector pixels along x and along y, each 1 .. 8 finite positive numbers, the longest first.
+    projRes : (width, height)
+        Of the projector, each 1 .. 65536.
+
+    Returns
+    -------
+    numpy.ndarray
+        uint8 ``[4 * (nx + ny), height, width]``.
+    """
+    tx, ty = _periods(periods)
+    w, h = _proj_res(projRes)[:2]
+    out = np.empty((4 * (len(tx) + len(ty)), h, w), np.uint8)
+    at = 0
+    for axis, vertical in ((tx, False), (ty, True)):
+        for T in axis:
+            for i in range(4):
+                out[at] = buildFringe(float(T), shift=i * float(T) / 4, dims=(w, h), vertical=vertical)
+                at += 1
+    return out
+
+
+def _phase_decode_args(stack, tx, ty, proj, thr2, mx, my, box):
+    x0, y0, w, h = box
+    n = 4 * (len(tx) + len(ty))
+    if int(stack.shape[0]) < n:
+        raise ValueError("%d x-periods and %d y-periods need %d images, got %d" % (len(tx), len(ty), n, int(stack.shape[0])))
+    if h * w >= 1 << 31 or int(stack.shape[1]) * int(stack.shape[2]) >= 1 << 31:
+        raise ValueError("images or regions of 2^31 pixels or more are not supported")
+    dp = ctypes.POINTER(ctypes.c_double)
+    return (_ptr(stack), n, int(stack.shape[1]), int(stack.shape[2]), _ptr(mx), _ptr(my), x0, y0, h, w, len(tx), len(ty),
+            tx.ctypes.data_as(dp), ty.ctypes.data_as(dp), proj[0], proj[1], thr2)
+
+
+def _phase_decode(stack, dev, args, h, w):
+    """-> float64 [h, w, 2] where the stack is; on its device's current stream for a tensor"""
+    if dev:
+        import torch
+        out = torch.empty((h, w, 2), dtype=torch.float64, device=stack.device)
+        if h * w:
+            _native.call_on_stream(stack, _native.lib().ssamd_phaseshift_decode_device, *args, out.data_ptr(), invalid=_INVALID)
+        return out
+    out = np.empty((h, w, 2), np.float64)
+    if h * w:
+        _native.check(_native.lib().ssamd_phaseshift_decode(*args, out.ctypes.data, -1), _INVALID)
+    return out
+
+
+def phaseShiftDecode(images, periods, projRes, maps=None, roi=None, min_modulation=None):
+    """
+    Decode a stack of four-step phase-shift images into a dense camera-to-projector map: the three closures of the
+    reference's ``calibration.phaseShift`` (``getPhase``, ``unwrap``, ``getProjCoord``, ``calibration.py:656-687`` and
+    ``:726-738``), which the reference samples at chessboard corners only, for every pixel of the region, by one HIP kernel
+    (``phaseshift_decode_kernel``).
+
+    Per set of four images ``I0 .. I3`` (``cos(theta + i pi / 2)`` expected): ``theta = mod(arctan2(I3 - I1, I0 - I2), 2 pi)``.
+    The first period of an axis gives the absolute phase; every later period ``T`` refines it against the first ``T0``
+    (heterodyne principle): ``k = rint((phi * T0 / T - theta) / (2 pi))``, ``phi = (theta + 2 pi k) * T / T0``.  Finally
+    ``px = width * phi_x / (2 pi)`` and ``py = height * phi_y / (2 pi)``: as ``getProjCoord`` scales by the projector's
+    resolution, not by the first period, the coordinates are pixels only when ``periods[v][0]`` equals the projector's extent
+    along that axis (the reference's behaviour; nothing is raised otherwise).  fp64, the reference's operations in its order;
+    ``arctan2`` is the device library's, so the result is close to numpy's, not bit-equal.
+
+    Parameters
+    ----------
+    images : ndarray or CUDA/HIP tensor uint8 ``[M, Hc, Wc]``, or a sequence of ``[Hc, Wc]`` uint8 arrays (stacked on the host)
+        In the order of :func:`phaseShiftPattern`.  ``M >= N = 4 * (nx + ny)``; only the first N are read, so the reference's
+        trailing image in normal light may stay in the stack.
+    periods : (list_x, list_y)
+        As the reference's: the periods of the fringes along x and along y, each 1 .. 8 finite positive numbers.
+    projRes : (width, height)
+        Of the projector, each 1 .. 65536.
+    maps : (mapx, mapy), optional
+        float32 ``[Hc, Wc]``: every image is sampled as :func:`grayCodeDecode` samples it.  Default: the images as they are.
+    roi : (x, y, width, height), optional
+        The region ``[y, y + height) x [x, x + width)``.  Default: the whole image.
+    min_modulation : number >= 0, optional
+        A pixel for which any set has ``sqrt((I3 - I1)^2 + (I0 - I2)^2) / 2 < min_modulation`` becomes (NaN, NaN).  The
+        test is made on integers, ``a^2 + b^2 < ceil(4 m^2)``.  Default None: no pixel is masked, as in the reference.
+
+    Returns
+    -------
+    ndarray or tensor
+        float64 ``[h, w, 2]``: ``(px, py)``.  A tensor on the images' device, computed on its current stream, for a tensor.
+    """
+    tx, ty = _periods(periods)
+    proj = _proj_res(projRes)
+    thr2 = _mod_thr2(min_modulation)
+    stack, dev = _gray_stack(images)
+    mx, my = _gray_maps(maps, stack, dev)
+    box = _roi(roi, (int(stack.shape[2]), int(stack.shape[1])))
+    args = _phase_decode_args(stack, tx, ty, proj, thr2, mx, my, box)
+    return _phase_decode(stack, dev, args, box[3], box[2])
+
+
+class PhaseShift:
+    """
+    A phase-shift scanner with a calibrated camera-projector rig: image stack in, dense cloud out, by two HIP kernels --
+    :func:`phaseShiftDecode` with the camera's undistortion maps fused in, then ``StructuredLightRig.triangulate`` on the
+    pixel grid.
+
+    Camera pixel ``(x, y)`` and projector point ``(px, py)`` carry no half-pixel offsets.  That is the convention of the
+    calibration routine whose formulae these are (``calibration.phaseShift`` pairs ``cornerSubPix`` coordinates, pixel centres
+    at integers, with ``width * phi / (2 pi)``).  A user of another convention decodes with :func:`phaseShiftDecode` and calls
+    ``StructuredLightRig.triangulate`` with points of their own.
+
+    Parameters
+    ----------
+    rig : StereoRig
+        Camera in position 1 (world origin), projector in position 2.  Held as a ``StructuredLightRig`` (``self.rig``).
+    periods : (list_x, list_y)
+        As :func:`phaseShiftDecode` takes them.
+    min_modulation : number >= 0, optional
+        As :func:`phaseShiftDecode` takes it.  Default None.
+    """
+
+    def __init__(self, rig, periods, min_modulation=None):
+        self.rig = rig if isinstance(rig, StructuredLightRig) else StructuredLightRig(rig)
+        self.periods = _periods(periods)
+        self.min_modulation = min_modulation
+        self._thr2 = _mod_thr2(min_modulation)
+        self._proj = _proj_res(self.rig.res2)
+        self._cache = self.rig._cache    # _cached_maps' entries, shared with the rig's undistortCameraImage
+
+    def getCloud(self, images, roi=None):
+        """
+        The dense cloud of a stack of phase-shift images.
+
+        Parameters
+        ----------
+        images : what :func:`phaseShiftDecode` takes
+            Of the rig's ``res1``, in the order of :func:`phaseShiftPattern`; any following extra image is ignored.
+        roi : (x, y, width, height), optional
+            Default None: the whole image.
+
+        Returns
+        -------
+        ndarray or tensor
+            float64 ``[h, w, 3]``, NaN at the masked pixels.  For a tensor a tensor on its device: the two kernels are queued
+            on the current stream and nothing is read back.
+        """
+        size = (int(self.rig.res1[0]), int(self.rig.res1[1]))
+        stack, dev = _gray_stack(images, size)
+        box = _roi(roi, size)
+        geom = self.rig._geometry()
+        mx, my = _cached_maps(self._cache, self.rig, stack.device if dev else None)
+        args = _phase_decode_args(stack, self.periods[0], self.periods[1], self._proj, self._thr2, mx, my, box)
+        x0, y0, w, h = box
+        proj = _phase_decode(stack, dev, args, h, w)
+        gp = geom.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        lib = _native.lib() if h * w else None
+        if dev:
+            import torch
+            out = torch.empty((h, w, 3), dtype=torch.float64, device=stack.device)
+            if h * w:
+                _native.call_on_stream(stack, lib.ssamd_sl_triangulate_device, None, proj.data_ptr(), h * w, w, x0, y0, gp, out.data_ptr(),
+                                       invalid=_INVALID)
+            return out
+        out = np.empty((h, w, 3), np.float64)
+        if h * w:
+            _native.check(lib.ssamd_sl_triangulate(None, proj.ctypes.data, h * w, w, x0, y0, gp, out.ctypes.data, -1), _INVALID)
+        return out

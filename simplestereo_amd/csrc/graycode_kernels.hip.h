@@ -134,40 +134,47 @@ __device__ __forceinline__ GrayWindow graycode_window(const GrayTaps (&taps)[GRA
     return win;
 }
 
+// One plane's values at a thread's four pixels, read in the mode fixed outside the plane loop (graycode_codes, and
+// phaseshift_coords of phaseshift_kernels.hip.h).
+template <int MODE>
+__device__ __forceinline__ void graycode_fetch(const uint8_t *__restrict__ pl, int wc, const bool (&live)[GRAYCODE_PER_THREAD],
+                                               const uint32_t (&at)[GRAYCODE_PER_THREAD], const GrayTaps *taps, const GrayWindow *win,
+                                               int (&v)[GRAYCODE_PER_THREAD])
+{
+    typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
+    typedef uint64_t __attribute__((aligned(1))) u64_unaligned;
+    if (MODE == GRAY_WINDOW) {
+        const uint64_t r0 = *reinterpret_cast<const u64_unaligned *>(pl + win->off);
+        const uint64_t r1 = *reinterpret_cast<const u64_unaligned *>(pl + win->off + wc);
+        const uint64_t r2 = *reinterpret_cast<const u64_unaligned *>(pl + win->off + 2 * wc);
+#pragma unroll
+        for (int j = 0; j < GRAYCODE_PER_THREAD; ++j) {
+            const GrayTaps &t = taps[j];
+            const uint32_t top = (uint32_t)((win->lower[j] ? r1 : r0) >> win->shift[j]), bot = (uint32_t)((win->lower[j] ? r2 : r1) >> win->shift[j]);
+            v[j] = (t.wt[0] * (int)(top & 0xffu) + t.wt[1] * (int)((top >> 8) & 0xffu) + t.wt[2] * (int)(bot & 0xffu) +
+                    t.wt[3] * (int)((bot >> 8) & 0xffu) + 512) >> 10;
+        }
+    } else if (MODE == GRAY_TAPS) {
+#pragma unroll
+        for (int j = 0; j < GRAYCODE_PER_THREAD; ++j) {
+            const GrayTaps &t = taps[j];
+            v[j] = (t.wt[0] * (int)pl[t.off[0]] + t.wt[1] * (int)pl[t.off[1]] + t.wt[2] * (int)pl[t.off[2]] + t.wt[3] * (int)pl[t.off[3]] + 512) >> 10;
+        }
+    } else if (MODE == GRAY_ROW4) {
+        const uint32_t q = *reinterpret_cast<const u32_unaligned *>(pl + at[0]);
+#pragma unroll
+        for (int j = 0; j < GRAYCODE_PER_THREAD; ++j) v[j] = (int)((q >> (8 * j)) & 0xffu);
+    } else {
+#pragma unroll
+        for (int j = 0; j < GRAYCODE_PER_THREAD; ++j) v[j] = live[j] ? (int)pl[at[j]] : 0;
+    }
+}
+
 template <int MODE>
 __device__ __forceinline__ void graycode_codes(const GrayDecodeArgs &A, const bool (&live)[GRAYCODE_PER_THREAD], const uint32_t (&at)[GRAYCODE_PER_THREAD],
                                                const GrayTaps *taps, const GrayWindow *win, int (&code)[2][GRAYCODE_PER_THREAD],
                                                bool (&err)[GRAYCODE_PER_THREAD])
 {
-    typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
-    typedef uint64_t __attribute__((aligned(1))) u64_unaligned;
-    auto fetch = [&](const uint8_t *__restrict__ pl, int (&v)[GRAYCODE_PER_THREAD]) {
-        if (MODE == GRAY_WINDOW) {
-            const uint64_t r0 = *reinterpret_cast<const u64_unaligned *>(pl + win->off);
-            const uint64_t r1 = *reinterpret_cast<const u64_unaligned *>(pl + win->off + A.wc);
-            const uint64_t r2 = *reinterpret_cast<const u64_unaligned *>(pl + win->off + 2 * A.wc);
-#pragma unroll
-            for (int j = 0; j < GRAYCODE_PER_THREAD; ++j) {
-                const GrayTaps &t = taps[j];
-                const uint32_t top = (uint32_t)((win->lower[j] ? r1 : r0) >> win->shift[j]), bot = (uint32_t)((win->lower[j] ? r2 : r1) >> win->shift[j]);
-                v[j] = (t.wt[0] * (int)(top & 0xffu) + t.wt[1] * (int)((top >> 8) & 0xffu) + t.wt[2] * (int)(bot & 0xffu) +
-                        t.wt[3] * (int)((bot >> 8) & 0xffu) + 512) >> 10;
-            }
-        } else if (MODE == GRAY_TAPS) {
-#pragma unroll
-            for (int j = 0; j < GRAYCODE_PER_THREAD; ++j) {
-                const GrayTaps &t = taps[j];
-                v[j] = (t.wt[0] * (int)pl[t.off[0]] + t.wt[1] * (int)pl[t.off[1]] + t.wt[2] * (int)pl[t.off[2]] + t.wt[3] * (int)pl[t.off[3]] + 512) >> 10;
-            }
-        } else if (MODE == GRAY_ROW4) {
-            const uint32_t q = *reinterpret_cast<const u32_unaligned *>(pl + at[0]);
-#pragma unroll
-            for (int j = 0; j < GRAYCODE_PER_THREAD; ++j) v[j] = (int)((q >> (8 * j)) & 0xffu);
-        } else {
-#pragma unroll
-            for (int j = 0; j < GRAYCODE_PER_THREAD; ++j) v[j] = live[j] ? (int)pl[at[j]] : 0;
-        }
-    };
     const uint8_t *pl = A.planes;
 #pragma unroll
     for (int j = 0; j < GRAYCODE_PER_THREAD; ++j) err[j] = false;
@@ -180,8 +187,8 @@ __device__ __forceinline__ void graycode_codes(const GrayDecodeArgs &A, const bo
 #pragma unroll(MODE == GRAY_ROW4 ? 4 : MODE == GRAY_WINDOW ? 2 : 1)
         for (int k = 0; k < nbits; ++k) {
             int v1[GRAYCODE_PER_THREAD], v2[GRAYCODE_PER_THREAD];
-            fetch(pl, v1);
-            fetch(pl + A.plane_stride, v2);
+            graycode_fetch<MODE>(pl, A.wc, live, at, taps, win, v1);
+            graycode_fetch<MODE>(pl + A.plane_stride, A.wc, live, at, taps, win, v2);
             pl += 2 * A.plane_stride;
 #pragma unroll
             for (int j = 0; j < GRAYCODE_PER_THREAD; ++j) {

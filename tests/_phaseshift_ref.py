@@ -1,0 +1,178 @@
+"""numpy restatement of phase shifting with heterodyne unwrapping -- the three closures of the reference's calibration.phaseShift
+(getPhase, unwrap, getProjCoord: calibration.py:656-687, :726-738) on every pixel -- and of StructuredLightRig
+(_rigs.py:631-715), the same chain in np.longdouble as a truth, and the seeded scenes of the phase-shift tests.  No simplestereo_amd, no cv2.
+
+The triangulation is the per-point function the FTP and Gray-code clouds end with (tests/_ftp_cloud_ref.py,
+tests/_graycode_ref.py) on points that carry no half-pixel offset."""
+import json
+import os
+
+import numpy as np
+
+import _ftp_cloud_ref as C
+import _graycode_ref as G
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+NPZ, JSON = os.path.join(GOLDEN, "phaseshift_cases.npz"), os.path.join(GOLDEN, "phaseshift_cases.json")
+MOD_ALL = 2 * 255 * 255 + 1
+
+
+# ------------------------------------------------------------------------------------------------ the decode
+def mod_thr2(min_modulation):
+    """sqrt(a^2 + b^2) / 2 < m on integers a, b  <=>  a^2 + b^2 < ceil(4 m^2)"""
+    if min_modulation is None:
+        return 0
+    return int(min(np.ceil(min(4.0 * float(min_modulation) * float(min_modulation), float(MOD_ALL))), MOD_ALL))
+
+
+def decode(stack, periods, proj_res, thr2=0, dtype=np.float64, details=False):
+    """`dtype` [H, W, 2]: (px, py) of the uint8 stack [>= 4 (nx + ny), H, W], (NaN, NaN) where a set's a^2 + b^2 < thr2.
+    np.float64 is the restatement, each operation in the reference's order; np.longdouble evaluates the same chain (its own
+    2 pi, its own k) as a truth.  details: also the worst |kk - rint(kk)| of every pixel over the heterodyne steps (0 without one)."""
+    two_pi = dtype(2) * (dtype(np.pi) if dtype is np.float64 else np.arctan2(dtype(0), dtype(-1)))
+    stack = np.asarray(stack)
+    shape = stack.shape[1:]
+    masked = np.zeros(shape, bool)
+    tie = np.zeros(shape, np.float64)
+    out = np.empty(shape + (2,), dtype)
+    i = 0
+    for v in range(2):
+        T0 = dtype(periods[v][0])
+        phase = None
+        for j, T in enumerate(periods[v]):
+            I = stack[i:i + 4].astype(np.int64)
+            i += 4
+            a, b = I[3] - I[1], I[0] - I[2]
+            masked |= a * a + b * b < thr2
+            theta = np.mod(np.arctan2(a.astype(dtype), b.astype(dtype)), two_pi)          # getPhase
+            if j == 0:
+                phase = theta
+            else:                                                                           # unwrap(phase, theta, T0, T)
+                kk = (phase * T0 / dtype(T) - theta) / two_pi
+                k = np.rint(kk)
+                tie = np.maximum(tie, np.abs(kk - k).astype(np.float64))
+                phase = (theta + two_pi * k) * dtype(T) / T0
+        out[..., v] = dtype(proj_res[v]) * phase / two_pi                                   # getProjCoord
+    out[masked] = np.nan
+    return (out, tie) if details else out
+
+
+def pattern(periods, proj_res):
+    """uint8 [4 (nx + ny), Hp, Wp]: buildFringe(T, shift=i T / 4, dims[, vertical]) of the reference (active.py:87-148), gray"""
+    w, h = proj_res
+    out = []
+    for v, n in ((0, w), (1, h)):
+        for T in periods[v]:
+            for i in range(4):
+                row = ((1 + np.cos(2 * np.pi * (1 / T) * (np.arange(n, dtype=float) + i * T / 4))) / 2) * 255
+                row = row.astype(np.uint8)
+                out.append(np.repeat(row[None, :], h, axis=0) if v == 0 else np.repeat(row[:, None], w, axis=1))
+    return np.stack(out)
+
+
+# ------------------------------------------------------------------------------------------------ the rig and the triangulation
+def sl_rig(rig):
+    """What the reference's StructuredLightRig holds for the rig dict `rig`: R1, R2, R (overwritten with the common orientation),
+    R_inv (4 x 4) and getBaseline() computed with that R; geom: the SSAMD_FTP_CLOUD_NGEOM doubles the triangulation reads."""
+    g = G.geometry(rig)
+    K2, T = np.array(rig["intrinsic2"], dtype=np.float64), np.array(rig["T"], dtype=np.float64).reshape(3, 1)
+    # the common orientation itself, as G.geometry builds it before inverting
+    Po2 = K2.dot(np.hstack((np.array(rig["R"], dtype=np.float64).reshape(3, 3), T)))
+    B = -np.linalg.inv(Po2[:, :3]).dot(Po2[:, 3])
+    v2 = np.cross([0, 0, 1], B)
+    v3 = np.cross(B, v2)
+    common = np.array([B / np.linalg.norm(B), v2 / np.linalg.norm(v2), v3 / np.linalg.norm(v3)])
+    Po2 = K2.dot(np.hstack((common, T)))                            # getBaseline() after `self.R = common`
+    baseline = np.linalg.norm(-np.linalg.inv(Po2[:, :3]).dot(Po2[:, 3]))
+    R_inv = np.eye(4)
+    R_inv[:3, :3] = np.linalg.inv(common)
+    g = g.copy()
+    g[67] = baseline
+    return {"R1": g[40:49].reshape(3, 3).copy(), "R2": g[49:58].reshape(3, 3).copy(), "R": common, "R_inv": R_inv, "baseline": float(baseline),
+            "geom": g}
+
+
+def triangulate(g, cam, proj, dtype=np.float64):
+    """`dtype` (n, 1, 3): StructuredLightRig.triangulate of cam, proj [..., 2] on the geometry g -- the lines of
+    _graycode_ref.cloud_dense with (u, v) = cam and (Xh, Yh) = proj as they are; three NaN where proj holds a NaN.  np.float64
+    on float64 points is the restatement; np.longdouble (on points of either precision) a truth."""
+    g = np.asarray(g, dtype=np.float64).astype(dtype)
+    cam, proj = (np.asarray(a).reshape(-1, 2).astype(dtype) for a in (cam, proj))      # (long doubles stay what they are)
+    u, v, Xh, Yh = cam[:, 0], cam[:, 1], proj[:, 0], proj[:, 1]
+    with np.errstate(all="ignore"):
+        hx, hy = C.undistort_points(g, Xh, Yh)
+        R1, R2, Ri, baseline = g[40:49], g[49:58], g[58:67], g[67]
+        ppx = ((R2[0] * hx + R2[1] * hy) + R2[2]) / ((R2[6] * hx + R2[7] * hy) + R2[8])
+        Wc = (R1[6] * u + R1[7] * v) + R1[8]
+        pcx = ((R1[0] * u + R1[1] * v) + R1[2]) / Wc
+        pcy = ((R1[3] * u + R1[4] * v) + R1[5]) / Wc
+        disparity = np.abs(ppx - pcx)
+        px, py, pz = baseline * (pcx / disparity), baseline * (pcy / disparity), baseline * (1 / disparity)
+        out = np.stack([(Ri[0] * px + Ri[1] * py) + Ri[2] * pz,
+                        (Ri[3] * px + Ri[4] * py) + Ri[5] * pz,
+                        (Ri[6] * px + Ri[7] * py) + Ri[8] * pz], axis=-1)
+    out[np.isnan(Xh) | np.isnan(Yh)] = np.nan
+    return out.reshape(-1, 1, 3)
+
+
+def grid(box):
+    """float64 [h, w, 2]: the camera pixels (x, y) of the region (x, y, width, height), integers"""
+    x0, y0, w, h = box
+    yy, xx = np.mgrid[0:h, 0:w]
+    return np.stack([xx + x0, yy + y0], axis=-1).astype(np.float64)
+
+
+def correspondences(rig, n, seed):
+    """n seeded camera points inside res1 and projector points inside res2, not on the grid: float64 [n, 2] each"""
+    rng = np.random.default_rng(seed)
+    (w1, h1), (w2, h2) = rig["res1"], rig["res2"]
+    cam = rng.random((n, 2)) * [w1 - 1, h1 - 1]
+    proj = np.stack([(cam[:, 0] / w1) * 0.7 * w2 + 0.15 * w2, rng.random(n) * (h2 - 1)], axis=-1) + rng.normal(0, 0.5, (n, 2))
+    return cam, proj
+
+
+# ------------------------------------------------------------------------------------------------ scenes
+LOW_BLOCK = (slice(4, 9), slice(10, 17))             # rows, columns of the weakly lit block (clipped to the image)
+
+
+def scene(seed, res1, res2, periods, amplitude=100, low=2, extra=1):
+    """The stack a camera of res1 sees of the phase-shift patterns on a smooth surface: pixel (y, x) looks at the projector point
+    p = an affine map plus a bump (seeded), rendered as rint(127.5 + A cos(2 pi p / T + i pi / 2)) with A = `amplitude`, and
+    A = `low` in LOW_BLOCK; `extra` planes of 255 follow (the image in normal light, ignored).  -> uint8 [4 (nx + ny) + extra, H, W]"""
+    rng = np.random.default_rng(seed)
+    (w1, h1), (w2, h2) = res1, res2
+    y, x = np.mgrid[0:h1, 0:w1].astype(np.float64)
+    cx, cy, s = rng.uniform(0.3, 0.7) * w1, rng.uniform(0.3, 0.7) * h1, 0.35 * max(w1, h1)
+    bump = np.exp(-((x - cx) ** 2 + (y - cy) ** 2) / (2 * s * s))
+    p = ((0.08 + 0.8 * x / w1 + 0.03 * y / h1) * w2 + 0.04 * w2 * bump, (0.07 + 0.02 * x / w1 + 0.82 * y / h1) * h2 + 0.05 * h2 * bump)
+    A = np.full((h1, w1), float(amplitude))
+    A[LOW_BLOCK] = low
+    planes = []
+    for v in range(2):
+        for T in periods[v]:
+            for i in range(4):
+                planes.append(np.rint(127.5 + A * np.cos(2 * np.pi * p[v] / T + i * np.pi / 2)))
+    planes += [np.full((h1, w1), 255.0)] * extra
+    return np.stack(planes).astype(np.uint8)
+
+
+def same_bits(got, want):
+    return G.same_points(got, want)
+
+
+_LOADED = []
+
+
+def load():
+    """(meta, arrays) of tests/golden/phaseshift_cases.{json,npz}, loaded once and shared, read-only"""
+    if not _LOADED:
+        with open(JSON) as f:
+            meta = json.load(f)
+        arrays = {}
+        with np.load(NPZ) as z:
+            for key in z.files:
+                a = z[key]
+                a.setflags(write=False)
+                arrays[key] = a
+        _LOADED.append((meta, arrays))
+    return _LOADED[0]
