@@ -574,6 +574,85 @@ class RectifiedStereoRig(StereoRig):
         return out
 
 
+# ------------------------------------------------------------------------------------------------ camera-projector geometry
+NGEOM = 68                # SSAMD_FTP_CLOUD_NGEOM
+
+
+def _low_level_rectify(rig):
+    """The rectifying transforms of Fusiello et al. for a camera at the world origin (the reference's ``_lowLevelRectify``,
+    ``rectification.py:271-302``): the new x axis along the baseline, y orthogonal to it and to the old z, no new intrinsics."""
+    ax = rig.getCenters()[1]
+    ay = np.cross([0, 0, 1], ax)
+    az = np.cross(ax, ay)
+    rot = np.array([ax / np.linalg.norm(ax), ay / np.linalg.norm(ay), az / np.linalg.norm(az)])
+    rect1 = rot.dot(np.linalg.inv(rig.intrinsic1))
+    rect2 = rot.dot(np.linalg.inv(rig.R)).dot(np.linalg.inv(rig.intrinsic2))
+    return rect1, rect2, rot
+
+
+def _r_inv4(common):
+    """The reference's 4 x 4 ``R_inv`` (``active.py:398-401``): the inverse of the common orientation, padded"""
+    R_inv = np.eye(4)
+    R_inv[:3, :3] = np.linalg.inv(common)
+    return R_inv
+
+
+def _triangulation_geom(rig, dist, rect1, rect2, common_inv):
+    """``geom`` with what the triangulation reads (``[12:37]`` and ``[40:68]``: K2, ``distCoeffs2``, the rectifying transforms, the
+    inverse common orientation, the baseline) and 0 elsewhere: the part all three geometry builders share"""
+    K2 = np.asarray(rig.intrinsic2, dtype=np.float64)
+    g = np.zeros(NGEOM)
+    g[12:16] = K2[0, 0], K2[1, 1], K2[0, 2], K2[1, 2]
+    g[16:28] = dist[:12]
+    g[28:37] = K2.ravel()
+    g[40:49] = rect1.ravel()
+    g[49:58] = rect2.ravel()
+    g[58:67] = common_inv.ravel()
+    g[67] = rig.getBaseline()
+    return g
+
+
+def _triangulation_geometry(rig, rect1, rect2, common_inv):
+    """The ``SSAMD_FTP_CLOUD_NGEOM`` doubles of a triangulation alone (``ssamd_graycode_cloud``, ``ssamd_sl_triangulate``):
+    :func:`_triangulation_geom` of the rig's own ``distCoeffs2`` and ``getBaseline()``, finite.  Neither the epipole nor a phase
+    period is in it, so ``T[2] == 0`` is fine."""
+    dist = _dist_vector(rig.distCoeffs2)                          # NotImplementedError for a tilted sensor; None is no distortion
+    g = _triangulation_geom(rig, dist, rect1, rect2, common_inv)
+    if not np.isfinite(g).all():
+        raise ValueError("the rig gives a geometry that is not finite")
+    return g
+
+
+def _undistort_maps(rig):
+    """float32 (mapx, mapy) of ``cv2.undistort(img, K1, distCoeffs1)``: ``initUndistortRectifyMap(K1, D1, I, K1, res1)``"""
+    return _init_undistort_rectify_map(rig.intrinsic1, rig.distCoeffs1, np.eye(3), rig.intrinsic1, rig.res1)
+
+
+def _cached_maps(cache, rig, device=None):
+    """The float32 (mapx, mapy) of ``cv2.undistort`` of a rig's camera, on the host (``device`` None) or as tensors on a device,
+    built on first use and kept in ``cache``, the dict ``StereoFTP``, ``GrayCode`` and ``StructuredLightRig`` hold per instance."""
+    if "host" not in cache:
+        cache["host"] = _undistort_maps(rig)
+    if device is None:
+        return cache["host"]
+    if "maps " + str(device) not in cache:
+        import torch
+        cache["maps " + str(device)] = tuple(torch.from_numpy(m).to(device) for m in cache["host"])
+    return cache["maps " + str(device)]
+
+
+def _undistort_device(cache, rig, img):
+    """``cv2.undistort(img, K1, distCoeffs1)`` of a contiguous uint8 ``[H, W, 3]`` device tensor: ``remap_bgr_kernel`` on the cached
+    maps of the rig's camera, on the tensor's current stream -> uint8 ``[res1 height, res1 width, 3]``"""
+    import torch
+    dmx, dmy = _cached_maps(cache, rig, img.device)
+    h, w = int(dmx.shape[0]), int(dmx.shape[1])
+    out = torch.empty((h, w, 3), dtype=torch.uint8, device=img.device)
+    _native.call_on_stream(img, _native.lib().ssamd_remap_bgr_device, img.data_ptr(), int(img.shape[0]), int(img.shape[1]),
+                           dmx.data_ptr(), dmy.data_ptr(), h, w, INTER_LINEAR, out.data_ptr())
+    return out
+
+
 class StructuredLightRig(StereoRig):
     """
     A camera-projector rig with the structured-light methods of ``simplestereo.StructuredLightRig`` (reference
@@ -598,10 +677,9 @@ class StructuredLightRig(StereoRig):
         self._computeMatrices()
 
     def _computeMatrices(self):
-        from .active import _low_level_rectify, _r_inv4
         self.R1, self.R2, self.R = _low_level_rectify(self)
         self.R_inv = _r_inv4(self.R)
-        self._cache = {}                          # active._cached_maps' entries: the camera's undistortion maps, per device
+        self._cache = {}                          # _cached_maps' entries: the camera's undistortion maps, per device
 
     @classmethod
     def fromFile(cls, filepath):
@@ -611,12 +689,7 @@ class StructuredLightRig(StereoRig):
     def _geometry(self):
         """The ``SSAMD_FTP_CLOUD_NGEOM`` doubles of ``ssamd_sl_triangulate``: K2, ``distCoeffs2``, ``R1``, ``R2``, the inverse common
         orientation and ``getBaseline()`` (computed with the overwritten ``R``)."""
-        from .active import _triangulation_geom
-        dist = _dist_vector(self.distCoeffs2)                      # NotImplementedError for a tilted sensor
-        g = _triangulation_geom(self, dist, self.R1, self.R2, self.R_inv[:3, :3])
-        if not np.isfinite(g).all():
-            raise ValueError("the rig gives a geometry that is not finite")
-        return g
+        return _triangulation_geometry(self, self.R1, self.R2, self.R_inv[:3, :3])
 
     @staticmethod
     def _points(p, name):
@@ -684,7 +757,6 @@ class StructuredLightRig(StereoRig):
         -------
         The undistorted image, of the rig's ``res1``, where the input is.
         """
-        from .active import _cached_maps
         if not _is_device_tensor(imgObj):
             mx, my = _cached_maps(self._cache, self)
             return _remap(imgObj, mx, my, INTER_LINEAR)
@@ -692,10 +764,5 @@ class StructuredLightRig(StereoRig):
         if imgObj.dtype != torch.uint8 or imgObj.dim() not in (2, 3) or (imgObj.dim() == 3 and imgObj.shape[2] != 3):
             raise ValueError("device undistortion expects a uint8 [H,W] or [H,W,3] tensor")
         gray = imgObj.dim() == 2
-        src = (imgObj.unsqueeze(2).expand(-1, -1, 3) if gray else imgObj).contiguous()
-        dmx, dmy = _cached_maps(self._cache, self, imgObj.device)
-        h, w = int(dmx.shape[0]), int(dmx.shape[1])
-        out = torch.empty((h, w, 3), dtype=torch.uint8, device=imgObj.device)
-        _native.call_on_stream(src, _native.lib().ssamd_remap_bgr_device, src.data_ptr(), int(src.shape[0]), int(src.shape[1]),
-                               dmx.data_ptr(), dmy.data_ptr(), h, w, INTER_LINEAR, out.data_ptr())
+        out = _undistort_device(self._cache, self, (imgObj.unsqueeze(2).expand(-1, -1, 3) if gray else imgObj).contiguous())
         return out[:, :, 0].contiguous() if gray else out

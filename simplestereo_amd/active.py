@@ -221,7 +221,8 @@ import os
 import numpy as np
 
 from . import _native
-from ._rigs import INTER_LINEAR, StructuredLightRig, _dist_vector, _distort, _init_undistort_rectify_map, _remap, _undistort_points
+from ._rigs import (INTER_LINEAR, NGEOM, StructuredLightRig, _cached_maps, _dist_vector, _distort, _low_level_rectify, _r_inv4, _remap,
+                    _triangulation_geom, _triangulation_geometry, _undistort_device, _undistort_points)
 from ._native import c_double as _c_double, is_device_tensor as _is_device_tensor
 
 __all__ = ["ftpPhase", "ftpCloud", "ftpFringeOrder", "ftpGeometry", "FtpGeometry", "MAX_WIDTH", "ftpReference",
@@ -376,9 +377,6 @@ def ftpCarrierPhase(img, fc, radius_factor=0.5, unwrap=None, tau=1):
 
 
 # ------------------------------------------------------------------------------------------------ phase -> point cloud
-NGEOM = 68                # SSAMD_FTP_CLOUD_NGEOM
-
-
 def _finite(v, what):
     v = _number(v, what)
     if not np.isfinite(v):
@@ -401,53 +399,6 @@ def _roi(roi, res1):
     if min(x, y, w, h) < 0 or x + w > W or y + h > H:
         raise ValueError("roi %s is not inside the camera image (%d x %d)" % ((x, y, w, h), W, H))
     return x, y, w, h
-
-
-def _low_level_rectify(rig):
-    """The rectifying transforms of Fusiello et al. for a camera at the world origin (the reference's ``_lowLevelRectify``,
-    ``rectification.py:271-302``): the new x axis along the baseline, y orthogonal to it and to the old z, no new intrinsics."""
-    ax = rig.getCenters()[1]
-    ay = np.cross([0, 0, 1], ax)
-    az = np.cross(ax, ay)
-    rot = np.array([ax / np.linalg.norm(ax), ay / np.linalg.norm(ay), az / np.linalg.norm(az)])
-    rect1 = rot.dot(np.linalg.inv(rig.intrinsic1))
-    rect2 = rot.dot(np.linalg.inv(rig.R)).dot(np.linalg.inv(rig.intrinsic2))
-    return rect1, rect2, rot
-
-
-def _r_inv4(common):
-    """The reference's 4 x 4 ``R_inv`` (``active.py:398-401``): the inverse of the common orientation, padded"""
-    R_inv = np.eye(4)
-    R_inv[:3, :3] = np.linalg.inv(common)
-    return R_inv
-
-
-def _triangulation_geom(rig, dist, rect1, rect2, common_inv):
-    """``geom`` with what the triangulation reads (``[12:37]`` and ``[40:68]``: K2, ``distCoeffs2``, the rectifying transforms, the
-    inverse common orientation, the baseline) and 0 elsewhere: the part all three geometry builders share"""
-    K2 = np.asarray(rig.intrinsic2, dtype=np.float64)
-    g = np.zeros(NGEOM)
-    g[12:16] = K2[0, 0], K2[1, 1], K2[0, 2], K2[1, 2]
-    g[16:28] = dist[:12]
-    g[28:37] = K2.ravel()
-    g[40:49] = rect1.ravel()
-    g[49:58] = rect2.ravel()
-    g[58:67] = common_inv.ravel()
-    g[67] = rig.getBaseline()
-    return g
-
-
-def _cached_maps(cache, rig, device=None):
-    """The float32 (mapx, mapy) of ``cv2.undistort`` of a rig's camera, on the host (``device`` None) or as tensors on a device,
-    built on first use and kept in ``cache``, the dict ``StereoFTP`` and ``GrayCode`` hold per instance."""
-    if "host" not in cache:
-        cache["host"] = _undistort_maps(rig)
-    if device is None:
-        return cache["host"]
-    if "maps " + str(device) not in cache:
-        import torch
-        cache["maps " + str(device)] = tuple(torch.from_numpy(m).to(device) for m in cache["host"])
-    return cache["maps " + str(device)]
 
 
 class FtpGeometry:
@@ -924,13 +875,7 @@ class StereoFTP:
         if not _is_device_tensor(img):
             mx, my = self._host_maps()
             return _remap(img, mx, my, INTER_LINEAR)
-        import torch
-        _, dmx, dmy = self._device_state(img.device)
-        h, w = int(dmx.shape[0]), int(dmx.shape[1])
-        out = torch.empty((h, w, 3), dtype=torch.uint8, device=img.device)
-        _native.call_on_stream(img, _native.lib().ssamd_remap_bgr_device, img.data_ptr(), int(img.shape[0]), int(img.shape[1]),
-                               dmx.data_ptr(), dmy.data_ptr(), h, w, INTER_LINEAR, out.data_ptr())
-        return out
+        return _undistort_device(self._cache, self.stereoRig, img)
 
     def _triangulate(self, camPoints, p_x, roi):
         """
@@ -1264,11 +1209,6 @@ class StereoFTP_PhaseOnly(StereoFTP):
 
 
 # ------------------------------------------------------------------------------------------------ Gray code
-def _undistort_maps(rig):
-    """float32 (mapx, mapy) of ``cv2.undistort(img, K1, distCoeffs1)``: ``initUndistortRectifyMap(K1, D1, I, K1, res1)``"""
-    return _init_undistort_rectify_map(rig.intrinsic1, rig.distCoeffs1, np.eye(3), rig.intrinsic1, rig.res1)
-
-
 def _integer(v):
     return isinstance(v, (numbers.Integral, np.integer)) and not isinstance(v, (bool, np.bool_))
 
@@ -1456,15 +1396,20 @@ def _gray_blocks(h, w):
     return (h * w + _native.GRAYCODE_BLOCK - 1) // _native.GRAYCODE_BLOCK
 
 
-def _gray_decode_args(stack, proj, thr, mx, my, box):
+def _stack_args(stack, n, mx, my, box):
+    """The ten arguments every decoder of a plane stack begins with: the first ``n`` planes, the maps (or None) and the region"""
     x0, y0, w, h = box
+    if h * w >= 1 << 31 or int(stack.shape[1]) * int(stack.shape[2]) >= 1 << 31:
+        raise ValueError("images or regions of 2^31 pixels or more are not supported")
+    return (_ptr(stack), n, int(stack.shape[1]), int(stack.shape[2]), _ptr(mx), _ptr(my), x0, y0, h, w)
+
+
+def _gray_decode_args(stack, proj, thr, mx, my, box):
     pw, ph, ncol, nrow = proj
     n = 2 * (ncol + nrow)
     if int(stack.shape[0]) < n:
         raise ValueError("a %d x %d projector needs %d pattern images, got %d" % (pw, ph, n, int(stack.shape[0])))
-    if h * w >= 1 << 31 or int(stack.shape[1]) * int(stack.shape[2]) >= 1 << 31:
-        raise ValueError("images or regions of 2^31 pixels or more are not supported")
-    return (_ptr(stack), n, int(stack.shape[1]), int(stack.shape[2]), _ptr(mx), _ptr(my), x0, y0, h, w, ncol, nrow, pw, ph, thr)
+    return _stack_args(stack, n, mx, my, box) + (ncol, nrow, pw, ph, thr)
 
 
 def _gray_decode_device(stack, args, h, w):
@@ -1559,12 +1504,7 @@ class GrayCode:
         """The ``SSAMD_FTP_CLOUD_NGEOM`` doubles of ``ssamd_graycode_cloud``: only what the triangulation reads -- K2,
         ``distCoeffs2``, the rectifying transforms, the inverse common orientation, the baseline.  Neither the epipole nor a
         phase period is in it, so ``T[2] == 0`` is fine."""
-        rig = self.rig
-        dist = _dist_vector(rig.distCoeffs2)                      # NotImplementedError for a tilted sensor; None is no distortion
-        g = _triangulation_geom(rig, dist, self.Rectify1, self.Rectify2, self.R_inv[:3, :3])
-        if not np.isfinite(g).all():
-            raise ValueError("the rig gives a geometry that is not finite")
-        return g
+        return _triangulation_geometry(self.rig, self.Rectify1, self.Rectify2, self.R_inv[:3, :3])
 
     def _load(self, paths, size):
         """The first ``num_patterns`` files as uint8 planes.  cv2's colour -> gray conversion is not restated: only 8-bit
@@ -1727,29 +1667,17 @@ def phaseShiftPattern(periods, projRes):
 
 
 def _phase_decode_args(stack, tx, ty, proj, thr2, mx, my, box):
-    x0, y0, w, h = box
     n = 4 * (len(tx) + len(ty))
     if int(stack.shape[0]) < n:
         raise ValueError("%d x-periods and %d y-periods need %d images, got %d" % (len(tx), len(ty), n, int(stack.shape[0])))
-    if h * w >= 1 << 31 or int(stack.shape[1]) * int(stack.shape[2]) >= 1 << 31:
-        raise ValueError("images or regions of 2^31 pixels or more are not supported")
     dp = ctypes.POINTER(ctypes.c_double)
-    return (_ptr(stack), n, int(stack.shape[1]), int(stack.shape[2]), _ptr(mx), _ptr(my), x0, y0, h, w, len(tx), len(ty),
-            tx.ctypes.data_as(dp), ty.ctypes.data_as(dp), proj[0], proj[1], thr2)
+    return _stack_args(stack, n, mx, my, box) + (len(tx), len(ty), tx.ctypes.data_as(dp), ty.ctypes.data_as(dp), proj[0], proj[1], thr2)
 
 
-def _phase_decode(stack, dev, args, h, w):
-    """-> float64 [h, w, 2] where the stack is; on its device's current stream for a tensor"""
-    if dev:
-        import torch
-        out = torch.empty((h, w, 2), dtype=torch.float64, device=stack.device)
-        if h * w:
-            _native.call_on_stream(stack, _native.lib().ssamd_phaseshift_decode_device, *args, out.data_ptr(), invalid=_INVALID)
-        return out
-    out = np.empty((h, w, 2), np.float64)
-    if h * w:
-        _native.check(_native.lib().ssamd_phaseshift_decode(*args, out.ctypes.data, -1), _INVALID)
-    return out
+def _phase_decode(stack, args, h, w):
+    """-> float64 [h, w, 2] where the stack is; on its device's current stream for a tensor.  ``args`` already hold the stack's
+    pointer (and the maps', which are of its kind)."""
+    return _native.run("ssamd_phaseshift_decode", (stack,), (h, w, 2), lambda _, out: args + (out,), _INVALID)
 
 
 def phaseShiftDecode(images, periods, projRes, maps=None, roi=None, min_modulation=None):
@@ -1796,7 +1724,7 @@ def phaseShiftDecode(images, periods, projRes, maps=None, roi=None, min_modulati
     mx, my = _gray_maps(maps, stack, dev)
     box = _roi(roi, (int(stack.shape[2]), int(stack.shape[1])))
     args = _phase_decode_args(stack, tx, ty, proj, thr2, mx, my, box)
-    return _phase_decode(stack, dev, args, box[3], box[2])
+    return _phase_decode(stack, args, box[3], box[2])
 
 
 class PhaseShift:
@@ -1852,17 +1780,6 @@ class PhaseShift:
         mx, my = _cached_maps(self._cache, self.rig, stack.device if dev else None)
         args = _phase_decode_args(stack, self.periods[0], self.periods[1], self._proj, self._thr2, mx, my, box)
         x0, y0, w, h = box
-        proj = _phase_decode(stack, dev, args, h, w)
+        proj = _phase_decode(stack, args, h, w)
         gp = geom.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-        lib = _native.lib() if h * w else None
-        if dev:
-            import torch
-            out = torch.empty((h, w, 3), dtype=torch.float64, device=stack.device)
-            if h * w:
-                _native.call_on_stream(stack, lib.ssamd_sl_triangulate_device, None, proj.data_ptr(), h * w, w, x0, y0, gp, out.data_ptr(),
-                                       invalid=_INVALID)
-            return out
-        out = np.empty((h, w, 3), np.float64)
-        if h * w:
-            _native.check(lib.ssamd_sl_triangulate(None, proj.ctypes.data, h * w, w, x0, y0, gp, out.ctypes.data, -1), _INVALID)
-        return out
+        return _native.run("ssamd_sl_triangulate", (proj,), (h, w, 3), lambda p, out: (None, p, h * w, w, x0, y0, gp, out), _INVALID)

@@ -9,7 +9,10 @@
 // the same partition, so a valid pixel's place in the compacted output is offset[block] + its rank inside the block -- counted
 // with ballots and popcounts within a wave and through LDS across the four waves: integers, plain stores, a fixed order, no
 // atomics, the same output on every run.
+// The decode's front is shared with phaseshift_decode_kernel (phaseshift_kernels.hip.h): PlaneStack, the arguments both begin
+// with, and plane_stack_frame, which finds a thread's pixels, taps and window and the mode its planes are read in (graycode_fetch).
 #pragma once
+#include <type_traits>
 #include "common.hip.h"
 #include "ftp_cloud_kernels.hip.h"
 
@@ -20,14 +23,21 @@ constexpr int GRAYCODE_WAVES = GRAYCODE_THREADS / 64;
 constexpr int GRAYCODE_PER_THREAD = 4;
 constexpr int GRAYCODE_BLOCK = GRAYCODE_THREADS * GRAYCODE_PER_THREAD;      // SSAMD_GRAYCODE_BLOCK of include/ssamd_graycode.h
 
-struct GrayDecodeArgs {
-    const uint8_t *planes;          // [n][hc][wc]; plane 2 k is bit k's pattern image, 2 k + 1 its inverse, columns first, MSB first
+// What every decoder of a plane stack is given: n gray planes of one camera, the undistortion maps they are sampled through (or
+// none) and the region to decode.  GrayDecodeArgs and PhaseShiftArgs (phaseshift_kernels.hip.h) begin with it; plane_stack_check
+// (host_graycode.h) fills it, plane_stack_frame reads it.
+struct PlaneStack {
+    const uint8_t *planes;          // [n][hc][wc]
     const float *mapx, *mapy;       // [hc][wc] undistortion maps (MAPS) or unused
-    int32_t *out;                   // [h][w][2]
-    int32_t *counts;                // [ceil(npix / GRAYCODE_BLOCK)] or NULL
     long long plane_stride;         // hc * wc < 2^31
     long long npix;                 // h * w < 2^31
     int hc, wc, x0, y0, w;
+};
+
+struct GrayDecodeArgs {
+    PlaneStack stack;               // plane 2 k is bit k's pattern image, 2 k + 1 its inverse, columns first, MSB first
+    int32_t *out;                   // [h][w][2]
+    int32_t *counts;                // [ceil(npix / GRAYCODE_BLOCK)] or NULL
     int ncol, nrow, pw, ph, thr;    // bits per code, projector size, white threshold 0 .. 256
 };
 
@@ -170,12 +180,43 @@ __device__ __forceinline__ void graycode_fetch(const uint8_t *__restrict__ pl, i
     }
 }
 
+// The front of a decoder: a thread's four pixels from p0 on -- live[j] if pixel p0 + j is inside the region, at[j] its offset inside
+// a plane (and inside the maps) --, with MAPS their taps and window, and the mode all planes are read in.  body(mode, at, taps, win)
+// runs once, with the mode as a compile-time constant (std::integral_constant): the plane loop of graycode_codes or
+// phaseshift_coords.  Without maps a thread whose four pixels are alive and consecutive bytes of a plane reads them with one load.
+template <bool MAPS, class Body>
+__device__ __forceinline__ void plane_stack_frame(const PlaneStack &S, long long p0, bool (&live)[GRAYCODE_PER_THREAD], Body body)
+{
+    uint32_t at[GRAYCODE_PER_THREAD];
+#pragma unroll
+    for (int j = 0; j < GRAYCODE_PER_THREAD; ++j) {
+        live[j] = p0 + j < S.npix;
+        const uint32_t p = live[j] ? (uint32_t)(p0 + j) : 0u;
+        const uint32_t ry = p / (uint32_t)S.w, rx = p - ry * (uint32_t)S.w;
+        at[j] = (uint32_t)(S.y0 + (int)ry) * (uint32_t)S.wc + (uint32_t)(S.x0 + (int)rx);
+    }
+    if (MAPS) {
+        GrayTaps taps[GRAYCODE_PER_THREAD];
+#pragma unroll
+        for (int j = 0; j < GRAYCODE_PER_THREAD; ++j)      // (a pixel past the end: no taps)
+            taps[j] = graycode_taps(live[j] ? S.mapx[at[j]] : __builtin_nanf(""), live[j] ? S.mapy[at[j]] : 0.f, S.hc, S.wc);
+        const GrayWindow win = graycode_window(taps, live, S.wc, S.plane_stride);
+        if (win.ok) body(std::integral_constant<int, GRAY_WINDOW>(), at, taps, &win);
+        else body(std::integral_constant<int, GRAY_TAPS>(), at, taps, nullptr);
+    } else if (live[GRAYCODE_PER_THREAD - 1] && at[GRAYCODE_PER_THREAD - 1] == at[0] + (GRAYCODE_PER_THREAD - 1)) {
+        body(std::integral_constant<int, GRAY_ROW4>(), at, nullptr, nullptr);
+    } else {
+        body(std::integral_constant<int, GRAY_BYTES>(), at, nullptr, nullptr);
+    }
+}
+
 template <int MODE>
 __device__ __forceinline__ void graycode_codes(const GrayDecodeArgs &A, const bool (&live)[GRAYCODE_PER_THREAD], const uint32_t (&at)[GRAYCODE_PER_THREAD],
                                                const GrayTaps *taps, const GrayWindow *win, int (&code)[2][GRAYCODE_PER_THREAD],
                                                bool (&err)[GRAYCODE_PER_THREAD])
 {
-    const uint8_t *pl = A.planes;
+    const PlaneStack &S = A.stack;
+    const uint8_t *pl = S.planes;
 #pragma unroll
     for (int j = 0; j < GRAYCODE_PER_THREAD; ++j) err[j] = false;
 #pragma unroll
@@ -187,9 +228,9 @@ __device__ __forceinline__ void graycode_codes(const GrayDecodeArgs &A, const bo
 #pragma unroll(MODE == GRAY_ROW4 ? 4 : MODE == GRAY_WINDOW ? 2 : 1)
         for (int k = 0; k < nbits; ++k) {
             int v1[GRAYCODE_PER_THREAD], v2[GRAYCODE_PER_THREAD];
-            graycode_fetch<MODE>(pl, A.wc, live, at, taps, win, v1);
-            graycode_fetch<MODE>(pl + A.plane_stride, A.wc, live, at, taps, win, v2);
-            pl += 2 * A.plane_stride;
+            graycode_fetch<MODE>(pl, S.wc, live, at, taps, win, v1);
+            graycode_fetch<MODE>(pl + S.plane_stride, S.wc, live, at, taps, win, v2);
+            pl += 2 * S.plane_stride;
 #pragma unroll
             for (int j = 0; j < GRAYCODE_PER_THREAD; ++j) {
                 const int d = v1[j] - v2[j];
@@ -214,30 +255,11 @@ __global__ __launch_bounds__(GRAYCODE_THREADS) void graycode_decode_kernel(const
 {
     __shared__ int wave_total[GRAYCODE_WAVES];
     const long long p0 = (long long)blockIdx.x * GRAYCODE_BLOCK + GRAYCODE_PER_THREAD * (int)threadIdx.x;
-    bool live[GRAYCODE_PER_THREAD];
-    uint32_t at[GRAYCODE_PER_THREAD];            // offset of the camera pixel inside a plane (and inside the maps)
-#pragma unroll
-    for (int j = 0; j < GRAYCODE_PER_THREAD; ++j) {
-        live[j] = p0 + j < A.npix;
-        const uint32_t p = live[j] ? (uint32_t)(p0 + j) : 0u;
-        const uint32_t ry = p / (uint32_t)A.w, rx = p - ry * (uint32_t)A.w;
-        at[j] = (uint32_t)(A.y0 + (int)ry) * (uint32_t)A.wc + (uint32_t)(A.x0 + (int)rx);
-    }
-    bool err[GRAYCODE_PER_THREAD];
+    bool live[GRAYCODE_PER_THREAD], err[GRAYCODE_PER_THREAD];
     int code[2][GRAYCODE_PER_THREAD];
-    if (MAPS) {
-        GrayTaps taps[GRAYCODE_PER_THREAD];
-#pragma unroll
-        for (int j = 0; j < GRAYCODE_PER_THREAD; ++j)      // (a pixel past the end: no taps)
-            taps[j] = graycode_taps(live[j] ? A.mapx[at[j]] : __builtin_nanf(""), live[j] ? A.mapy[at[j]] : 0.f, A.hc, A.wc);
-        const GrayWindow win = graycode_window(taps, live, A.wc, A.plane_stride);
-        if (win.ok) graycode_codes<GRAY_WINDOW>(A, live, at, taps, &win, code, err);
-        else graycode_codes<GRAY_TAPS>(A, live, at, taps, nullptr, code, err);
-    } else if (live[GRAYCODE_PER_THREAD - 1] && at[GRAYCODE_PER_THREAD - 1] == at[0] + (GRAYCODE_PER_THREAD - 1)) {
-        graycode_codes<GRAY_ROW4>(A, live, at, nullptr, nullptr, code, err);      // all alive and consecutive bytes of a plane
-    } else {
-        graycode_codes<GRAY_BYTES>(A, live, at, nullptr, nullptr, code, err);
-    }
+    plane_stack_frame<MAPS>(A.stack, p0, live, [&](auto mode, const uint32_t (&at)[GRAYCODE_PER_THREAD], const GrayTaps *taps, const GrayWindow *win) {
+        graycode_codes<decltype(mode)::value>(A, live, at, taps, win, code, err);
+    });
     bool valid[GRAYCODE_PER_THREAD];
     int2 px[GRAYCODE_PER_THREAD];
 #pragma unroll

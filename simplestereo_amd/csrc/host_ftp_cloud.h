@@ -36,6 +36,19 @@ int ftp_pointwise_launch(Ctx &c, const Kernel (&kernels)[4], const double *d_pha
     return SSAMD_OK;
 }
 
+// The instance of a kernel template for a distortion model 0 .. 3, where one launch names it:
+//   model_instance(model, [](auto m) { return kernel<decltype(m)::value>; })
+template <class Of>
+auto model_instance(int model, Of of) -> decltype(of(std::integral_constant<int, 0>()))
+{
+    switch (model & 3) {
+    case 0: return of(std::integral_constant<int, 0>());
+    case 1: return of(std::integral_constant<int, 1>());
+    case 2: return of(std::integral_constant<int, 2>());
+    default: return of(std::integral_constant<int, 3>());
+    }
+}
+
 constexpr decltype(&ftp_cloud_kernel<0>) FTP_CLOUD_KERNELS[4] = {ftp_cloud_kernel<0>, ftp_cloud_kernel<1>, ftp_cloud_kernel<2>, ftp_cloud_kernel<3>};
 
 // FTP phase -> cloud: the checks shared by the host and the device entry point; fills the by-value geometry (all of it is read), the

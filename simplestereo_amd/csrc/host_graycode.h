@@ -1,37 +1,54 @@
-// Host section of ssamd_api.hip: Gray-code structured light (graycode_kernels.hip.h, include/ssamd_graycode.h) -- checks, launches, entry points.
+// Host section of ssamd_api.hip: Gray-code structured light (graycode_kernels.hip.h, include/ssamd_graycode.h) -- checks, launches, entry
+// points -- and what it shares with the phase-shift decoder (host_phaseshift.h): the check of a plane stack (plane_stack_check and
+// three one-line checks) and its staging for the host entry points (PlaneStaging).
 namespace {
 static_assert(SSAMD_GRAYCODE_BLOCK == GRAYCODE_BLOCK, "block size of ssamd_graycode.h");
 
-struct GrayShape {       // what the decode arguments come to once checked
-    long long plane, npix;
-    int nblocks;
-};
+inline int gray_blocks(long long npix) { return (int)((npix + GRAYCODE_BLOCK - 1) / GRAYCODE_BLOCK); }
 
-int graycode_region_check(int h, int w, int x0, int y0, GrayShape &S)
+int region_check(int h, int w, int x0, int y0, long long &npix)
 {
     if (h < 0 || w < 0 || x0 < 0 || y0 < 0) return fail(SSAMD_EINVAL, "Wrong region dimensions or origin!");
-    S.npix = (long long)h * w;
-    if (S.npix >= (1ll << 31)) return fail(SSAMD_EINVAL, "region of %d x %d pixels: 2^31 or more", h, w);
-    S.nblocks = (int)((S.npix + GRAYCODE_BLOCK - 1) / GRAYCODE_BLOCK);
+    npix = (long long)h * w;
+    if (npix >= (1ll << 31)) return fail(SSAMD_EINVAL, "region of %d x %d pixels: 2^31 or more", h, w);
     return SSAMD_OK;
 }
 
-int graycode_decode_check(const void *planes, int n, int hc, int wc, const void *mapx, const void *mapy, int x0, int y0, int h, int w,
-                          int ncol, int nrow, int pw, int ph, int thr, GrayShape &S)
+// the region, the images and the region inside the images -> S, with the caller's pointers (of the host or of the device)
+int plane_stack_check(const void *planes, int hc, int wc, const void *mapx, const void *mapy, int x0, int y0, int h, int w, PlaneStack &S)
 {
-    int rc = graycode_region_check(h, w, x0, y0, S);
+    int rc = region_check(h, w, x0, y0, S.npix);
     if (rc) return rc;
     if (hc < 0 || wc < 0) return fail(SSAMD_EINVAL, "Wrong image dimensions!");
-    S.plane = (long long)hc * wc;
-    if (S.plane >= (1ll << 31)) return fail(SSAMD_EINVAL, "pattern images of %d x %d pixels: 2^31 or more", hc, wc);
+    S.plane_stride = (long long)hc * wc;
+    if (S.plane_stride >= (1ll << 31)) return fail(SSAMD_EINVAL, "pattern images of %d x %d pixels: 2^31 or more", hc, wc);
     if ((long long)x0 + w > wc || (long long)y0 + h > hc)
         return fail(SSAMD_EINVAL, "region %d x %d at (%d, %d) leaves the pattern images (%d x %d)", w, h, x0, y0, wc, hc);
+    S.planes = (const uint8_t *)planes; S.mapx = (const float *)mapx; S.mapy = (const float *)mapy;
+    S.hc = hc; S.wc = wc; S.x0 = x0; S.y0 = y0; S.w = w;
+    return SSAMD_OK;
+}
+
+int projector_check(int pw, int ph)
+{
+    return pw < 1 || ph < 1 || pw > 65536 || ph > 65536 ? fail(SSAMD_EINVAL, "projector size %d x %d outside 1 .. 65536", pw, ph) : SSAMD_OK;
+}
+int maps_check(const PlaneStack &S) { return (S.mapx == nullptr) != (S.mapy == nullptr) ? fail(SSAMD_EINVAL, "mapx and mapy: both or neither") : SSAMD_OK; }
+int planes_check(const PlaneStack &S, int n) { return !S.planes && n > 0 && S.npix > 0 ? fail(SSAMD_EINVAL, "NULL buffer") : SSAMD_OK; }
+
+// the decode arguments once checked: everything of GrayDecodeArgs but `out` and `counts`
+int graycode_decode_check(const void *planes, int n, int hc, int wc, const void *mapx, const void *mapy, int x0, int y0, int h, int w,
+                          int ncol, int nrow, int pw, int ph, int thr, GrayDecodeArgs &A)
+{
+    A = GrayDecodeArgs{};
+    int rc = plane_stack_check(planes, hc, wc, mapx, mapy, x0, y0, h, w, A.stack);
+    if (rc) return rc;
     if (ncol < 0 || nrow < 0 || ncol > 16 || nrow > 16) return fail(SSAMD_EINVAL, "ncol and nrow must be in 0 .. 16 (%d, %d)", ncol, nrow);
     if (n != 2 * (ncol + nrow)) return fail(SSAMD_EINVAL, "%d pattern images for %d column and %d row bits: must be %d", n, ncol, nrow, 2 * (ncol + nrow));
-    if (pw < 1 || ph < 1 || pw > 65536 || ph > 65536) return fail(SSAMD_EINVAL, "projector size %d x %d outside 1 .. 65536", pw, ph);
+    if ((rc = projector_check(pw, ph))) return rc;
     if (thr < 0 || thr > 256) return fail(SSAMD_EINVAL, "white_thr must be in 0 .. 256");
-    if ((mapx == nullptr) != (mapy == nullptr)) return fail(SSAMD_EINVAL, "mapx and mapy: both or neither");
-    if (!planes && n > 0 && S.npix > 0) return fail(SSAMD_EINVAL, "NULL buffer");
+    if ((rc = maps_check(A.stack)) || (rc = planes_check(A.stack, n))) return rc;
+    A.ncol = ncol; A.nrow = nrow; A.pw = pw; A.ph = ph; A.thr = thr;
     return SSAMD_OK;
 }
 
@@ -42,14 +59,12 @@ int graycode_geom_check(const double *geom, FtpCloudGeom &G, int &model)
     return ftp_load_geom(geom, {{12, 37}, {40, SSAMD_FTP_CLOUD_NGEOM}}, G, model);
 }
 
-int graycode_decode_launch(Ctx &c, const uint8_t *d_planes, int hc, int wc, const float *d_mapx, const float *d_mapy, int x0, int y0, int w,
-                           int ncol, int nrow, int pw, int ph, int thr, const GrayShape &S, int32_t *d_out, int32_t *d_counts, hipStream_t s)
+int graycode_decode_launch(Ctx &c, const GrayDecodeArgs &A, hipStream_t s)
 {
-    if ((uintptr_t)d_out & 15) return fail(SSAMD_EINVAL, "the decoded buffer must be 16-byte aligned");
-    if (((uintptr_t)d_counts | (uintptr_t)d_mapx | (uintptr_t)d_mapy) & 3) return fail(SSAMD_EINVAL, "maps and counts must be 4-byte aligned");
-    const GrayDecodeArgs A{d_planes, d_mapx, d_mapy, d_out, d_counts, S.plane, S.npix, hc, wc, x0, y0, w, ncol, nrow, pw, ph, thr};
+    if ((uintptr_t)A.out & 15) return fail(SSAMD_EINVAL, "the decoded buffer must be 16-byte aligned");
+    if (((uintptr_t)A.counts | (uintptr_t)A.stack.mapx | (uintptr_t)A.stack.mapy) & 3) return fail(SSAMD_EINVAL, "maps and counts must be 4-byte aligned");
     Timed t(c, s, SSAMD_K_FTP);
-    hipLaunchKernelGGL(d_mapx ? graycode_decode_kernel<true> : graycode_decode_kernel<false>, dim3(S.nblocks), dim3(GRAYCODE_THREADS), 0, s, A);
+    hipLaunchKernelGGL(A.stack.mapx ? graycode_decode_kernel<true> : graycode_decode_kernel<false>, dim3(gray_blocks(A.stack.npix)), dim3(GRAYCODE_THREADS), 0, s, A);
     HIP_TRY(hipGetLastError());
     return SSAMD_OK;
 }
@@ -63,57 +78,78 @@ int graycode_scan_launch(Ctx &c, const int32_t *d_counts, int nblocks, int32_t *
     return SSAMD_OK;
 }
 
-int graycode_cloud_launch(Ctx &c, const int32_t *d_decoded, int w, int x0, int y0, const GrayShape &S, const FtpCloudGeom &G, int model,
+int graycode_cloud_launch(Ctx &c, const int32_t *d_decoded, long long npix, int w, int x0, int y0, const FtpCloudGeom &G, int model,
                           const int32_t *d_offsets, double *d_out, hipStream_t s)
 {
     if ((uintptr_t)d_decoded & 15) return fail(SSAMD_EINVAL, "the decoded buffer must be 16-byte aligned");
     if (((uintptr_t)d_out & 7) || ((uintptr_t)d_offsets & 3)) return fail(SSAMD_EINVAL, "points must be 8-byte and offsets 4-byte aligned");
     Timed t(c, s, SSAMD_K_REPROJECT);
-    static constexpr decltype(&graycode_cloud_kernel<0>) kernels[4] = {graycode_cloud_kernel<0>, graycode_cloud_kernel<1>,
-                                                                       graycode_cloud_kernel<2>, graycode_cloud_kernel<3>};
-    hipLaunchKernelGGL(kernels[model & 3], dim3(S.nblocks), dim3(GRAYCODE_THREADS), 0, s, d_decoded, d_offsets, d_out, S.npix, w, x0, y0, G);
+    hipLaunchKernelGGL(model_instance(model, [](auto m) { return graycode_cloud_kernel<decltype(m)::value>; }), dim3(gray_blocks(npix)), dim3(GRAYCODE_THREADS),
+                       0, s, d_decoded, d_offsets, d_out, npix, w, x0, y0, G);
     HIP_TRY(hipGetLastError());
     return SSAMD_OK;
 }
 
-// where the host forms keep things in the context's two staging buffers: planes, mapx, mapy in uwIn; counts, offsets, the decoded
-// pixels and the points in uwOut, each at a multiple of 256 bytes
+// Where the host forms keep things in the context's two staging buffers, each at a multiple of 256 bytes.  uwIn: the planes, mapx
+// and mapy of a checked stack S (host pointers); an absent input is 0 bytes of any address, and the buffer exists even without
+// planes (+ 1).  on_device: S with the staged pointers, the maps nullptr when absent.
 inline size_t gray_round(size_t b) { return (b + 255) & ~(size_t)255; }
-struct GrayStaging {
-    size_t planes, mapx, mapy;                 // uwIn (planes at 0)
-    size_t counts, offsets, decoded, points;   // uwOut (counts at 0)
-    GrayStaging(int n, const GrayShape &S)
+struct PlaneStaging {
+    HostIn planes, mapx, mapy;
+    PlaneStaging(const PlaneStack &S, int n)
     {
-        planes = 0;
-        mapx = gray_round((size_t)n * S.plane + 1);      // (+ 1: the buffer exists even without planes)
-        mapy = mapx + gray_round((size_t)S.plane * sizeof(float));
-        counts = 0;
-        offsets = gray_round((size_t)S.nblocks * sizeof(int32_t));
-        decoded = offsets + gray_round(((size_t)S.nblocks + 1) * sizeof(int32_t));
-        points = decoded + gray_round((size_t)S.npix * 2 * sizeof(int32_t));
+        const size_t plane_bytes = (size_t)n * S.plane_stride, map_bytes = S.mapx ? (size_t)S.plane_stride * sizeof(float) : 0;
+        const size_t at_mapx = gray_round(plane_bytes + 1);
+        planes = HostIn{&Ctx::uwIn, plane_bytes ? (const void *)S.planes : this, plane_bytes, 0};
+        mapx = HostIn{&Ctx::uwIn, map_bytes ? (const void *)S.mapx : this, map_bytes, at_mapx};
+        mapy = HostIn{&Ctx::uwIn, map_bytes ? (const void *)S.mapy : this, map_bytes, at_mapx + gray_round(map_bytes)};
+    }
+    PlaneStack on_device(Ctx &c, PlaneStack S) const
+    {
+        S.planes = (const uint8_t *)staged(c, &Ctx::uwIn, planes.at);
+        S.mapx = mapx.bytes ? (const float *)staged(c, &Ctx::uwIn, mapx.at) : nullptr;
+        S.mapy = mapy.bytes ? (const float *)staged(c, &Ctx::uwIn, mapy.at) : nullptr;
+        return S;
     }
 };
+// uwOut of the Gray-code host forms: counts, offsets, the decoded pixels and the points
+struct GrayStaging {
+    size_t counts, offsets, decoded, points;
+    explicit GrayStaging(long long npix)
+    {
+        const size_t nblocks = (size_t)gray_blocks(npix);
+        counts = 0;
+        offsets = gray_round(nblocks * sizeof(int32_t));
+        decoded = offsets + gray_round((nblocks + 1) * sizeof(int32_t));
+        points = decoded + gray_round((size_t)npix * 2 * sizeof(int32_t));
+    }
+};
+
+// the checked decode on the staged inputs of a host form: the decoded pixels and the counts go to their places in uwOut
+int graycode_decode_staged(Ctx &c, GrayDecodeArgs A, const PlaneStaging &in, const GrayStaging &at, hipStream_t s)
+{
+    A.stack = in.on_device(c, A.stack);
+    A.out = (int32_t *)staged(c, &Ctx::uwOut, at.decoded);
+    A.counts = (int32_t *)staged(c, &Ctx::uwOut, at.counts);
+    return graycode_decode_launch(c, A, s);
+}
 }  // namespace
 
 extern "C" {
 int ssamd_graycode_decode(const uint8_t *planes, int n, int hc, int wc, const float *mapx, const float *mapy, int x0, int y0, int h, int w,
                           int ncol, int nrow, int proj_w, int proj_h, int white_thr, int32_t *out, int32_t *counts, int device)
 {
-    GrayShape S;
-    int rc = graycode_decode_check(planes, n, hc, wc, mapx, mapy, x0, y0, h, w, ncol, nrow, proj_w, proj_h, white_thr, S);
-    if (rc || S.npix == 0) return rc;
+    GrayDecodeArgs A;
+    int rc = graycode_decode_check(planes, n, hc, wc, mapx, mapy, x0, y0, h, w, ncol, nrow, proj_w, proj_h, white_thr, A);
+    const long long npix = A.stack.npix;
+    if (rc || npix == 0) return rc;
     if (!out) return fail(SSAMD_EINVAL, "NULL buffer");
-    const GrayStaging at(n, S);
-    const size_t plane_bytes = (size_t)n * S.plane, map_bytes = mapx ? (size_t)S.plane * sizeof(float) : 0;      // (an absent input: 0 bytes of any address)
-    return host_route(device, {{&Ctx::uwIn, plane_bytes ? (const void *)planes : &at, plane_bytes, at.planes}, {&Ctx::uwIn, map_bytes ? (const void *)mapx : &at, map_bytes, at.mapx},
-                       {&Ctx::uwIn, map_bytes ? (const void *)mapy : &at, map_bytes, at.mapy}},
-                      {&Ctx::uwOut, out, (size_t)S.npix * 2 * sizeof(int32_t), at.decoded}, [&](Ctx &c, hipStream_t s) {
-        int32_t *const d_counts = (int32_t *)staged(c, &Ctx::uwOut, at.counts);
-        int r = graycode_decode_launch(c, (const uint8_t *)staged(c, &Ctx::uwIn, at.planes), hc, wc,
-                                       mapx ? (const float *)staged(c, &Ctx::uwIn, at.mapx) : nullptr, mapx ? (const float *)staged(c, &Ctx::uwIn, at.mapy) : nullptr,
-                                       x0, y0, w, ncol, nrow, proj_w, proj_h, white_thr, S, (int32_t *)staged(c, &Ctx::uwOut, at.decoded), d_counts, s);
+    const PlaneStaging in(A.stack, n);
+    const GrayStaging at(npix);
+    return host_route(device, {in.planes, in.mapx, in.mapy}, {&Ctx::uwOut, out, (size_t)npix * 2 * sizeof(int32_t), at.decoded}, [&](Ctx &c, hipStream_t s) {
+        int r = graycode_decode_staged(c, A, in, at, s);
         if (r) return r;
-        if (counts) HIP_TRY(hipMemcpyAsync(counts, d_counts, (size_t)S.nblocks * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (counts) HIP_TRY(hipMemcpyAsync(counts, staged(c, &Ctx::uwOut, at.counts), (size_t)gray_blocks(npix) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         return SSAMD_OK;
     });
 }
@@ -122,14 +158,14 @@ int ssamd_graycode_decode_device(const uint8_t *d_planes, int n, int hc, int wc,
                                  int h, int w, int ncol, int nrow, int proj_w, int proj_h, int white_thr, int32_t *d_out, int32_t *d_counts,
                                  void *stream)
 {
-    GrayShape S;
-    int rc = graycode_decode_check(d_planes, n, hc, wc, d_mapx, d_mapy, x0, y0, h, w, ncol, nrow, proj_w, proj_h, white_thr, S);
-    if (rc || S.npix == 0) return rc;
+    GrayDecodeArgs A;
+    int rc = graycode_decode_check(d_planes, n, hc, wc, d_mapx, d_mapy, x0, y0, h, w, ncol, nrow, proj_w, proj_h, white_thr, A);
+    if (rc || A.stack.npix == 0) return rc;
     if (!d_out) return fail(SSAMD_EINVAL, "NULL buffer");
+    A.out = d_out; A.counts = d_counts;
     CtxLock c;
     if ((rc = get_ctx(-1, c))) return rc;
-    return graycode_decode_launch(*c, d_planes, hc, wc, d_mapx, d_mapy, x0, y0, w, ncol, nrow, proj_w, proj_h, white_thr, S, d_out, d_counts,
-                                  (hipStream_t)stream);      // no scratch: nothing to order
+    return graycode_decode_launch(*c, A, (hipStream_t)stream);      // no scratch: nothing to order
 }
 
 int ssamd_graycode_offsets(const int32_t *counts, int nblocks, int32_t *offsets, int device)
@@ -157,32 +193,30 @@ int ssamd_graycode_cloud(const uint8_t *planes, int n, int hc, int wc, const flo
                          int ncol, int nrow, int proj_w, int proj_h, int white_thr, const double *geom, int dense, double *out, int *npoints,
                          int device)
 {
-    GrayShape S;
+    GrayDecodeArgs A;
     FtpCloudGeom G;
     int model;
-    int rc = graycode_decode_check(planes, n, hc, wc, mapx, mapy, x0, y0, h, w, ncol, nrow, proj_w, proj_h, white_thr, S);
+    int rc = graycode_decode_check(planes, n, hc, wc, mapx, mapy, x0, y0, h, w, ncol, nrow, proj_w, proj_h, white_thr, A);
     if (rc || (rc = graycode_geom_check(geom, G, model))) return rc;
     if (!npoints) return fail(SSAMD_EINVAL, "NULL buffer");
     *npoints = 0;
-    if (S.npix == 0) return SSAMD_OK;
+    const long long npix = A.stack.npix;
+    if (npix == 0) return SSAMD_OK;
     if (!out) return fail(SSAMD_EINVAL, "NULL buffer");
-    const GrayStaging at(n, S);
-    const size_t plane_bytes = (size_t)n * S.plane, map_bytes = mapx ? (size_t)S.plane * sizeof(float) : 0;      // (an absent input: 0 bytes of any address)
+    const PlaneStaging in(A.stack, n);
+    const GrayStaging at(npix);
     // the route reserves room for every pixel and copies down what `result.bytes` says once the launches are queued: the total is
     // known by then, because the compacted form waits for it to size the copy
-    HostOut result{&Ctx::uwOut, out, (size_t)S.npix * 3 * sizeof(double), at.points};
+    HostOut result{&Ctx::uwOut, out, (size_t)npix * 3 * sizeof(double), at.points};
     int total = 0;
-    rc = host_route(device, {{&Ctx::uwIn, plane_bytes ? (const void *)planes : &at, plane_bytes, at.planes}, {&Ctx::uwIn, map_bytes ? (const void *)mapx : &at, map_bytes, at.mapx},
-                       {&Ctx::uwIn, map_bytes ? (const void *)mapy : &at, map_bytes, at.mapy}},
-                    result, [&](Ctx &c, hipStream_t s) {
+    rc = host_route(device, {in.planes, in.mapx, in.mapy}, result, [&](Ctx &c, hipStream_t s) {
         int32_t *const d_counts = (int32_t *)staged(c, &Ctx::uwOut, at.counts), *const d_offsets = (int32_t *)staged(c, &Ctx::uwOut, at.offsets);
         int32_t *const d_decoded = (int32_t *)staged(c, &Ctx::uwOut, at.decoded);
-        int r = graycode_decode_launch(c, (const uint8_t *)staged(c, &Ctx::uwIn, at.planes), hc, wc,
-                                       mapx ? (const float *)staged(c, &Ctx::uwIn, at.mapx) : nullptr, mapx ? (const float *)staged(c, &Ctx::uwIn, at.mapy) : nullptr,
-                                       x0, y0, w, ncol, nrow, proj_w, proj_h, white_thr, S, d_decoded, d_counts, s);
-        if (r || (r = graycode_scan_launch(c, d_counts, S.nblocks, d_offsets, s))) return r;
-        if ((r = graycode_cloud_launch(c, d_decoded, w, x0, y0, S, G, model, dense ? nullptr : d_offsets, (double *)staged(c, &Ctx::uwOut, at.points), s))) return r;
-        HIP_TRY(hipMemcpyAsync(&total, d_offsets + S.nblocks, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        const int nblocks = gray_blocks(npix);
+        int r = graycode_decode_staged(c, A, in, at, s);
+        if (r || (r = graycode_scan_launch(c, d_counts, nblocks, d_offsets, s))) return r;
+        if ((r = graycode_cloud_launch(c, d_decoded, npix, w, x0, y0, G, model, dense ? nullptr : d_offsets, (double *)staged(c, &Ctx::uwOut, at.points), s))) return r;
+        HIP_TRY(hipMemcpyAsync(&total, d_offsets + nblocks, sizeof(int32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         if (!dense) result.bytes = (size_t)total * 3 * sizeof(double);
         return SSAMD_OK;
@@ -195,15 +229,15 @@ int ssamd_graycode_cloud(const uint8_t *planes, int n, int hc, int wc, const flo
 int ssamd_graycode_cloud_device(const int32_t *d_decoded, int h, int w, int x0, int y0, const double *geom, const int32_t *d_offsets,
                                 double *d_out, void *stream)
 {
-    GrayShape S;
+    long long npix;
     FtpCloudGeom G;
     int model;
-    int rc = graycode_region_check(h, w, x0, y0, S);
+    int rc = region_check(h, w, x0, y0, npix);
     if (rc || (rc = graycode_geom_check(geom, G, model))) return rc;
-    if (S.npix == 0) return SSAMD_OK;
+    if (npix == 0) return SSAMD_OK;
     if (!d_decoded || !d_out) return fail(SSAMD_EINVAL, "NULL buffer");
     CtxLock c;
     if ((rc = get_ctx(-1, c))) return rc;
-    return graycode_cloud_launch(*c, d_decoded, w, x0, y0, S, G, model, d_offsets, d_out, (hipStream_t)stream);
+    return graycode_cloud_launch(*c, d_decoded, npix, w, x0, y0, G, model, d_offsets, d_out, (hipStream_t)stream);
 }
 }  // extern "C"

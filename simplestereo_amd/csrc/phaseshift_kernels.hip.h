@@ -3,9 +3,10 @@
 // (_rigs.py:654-700) for correspondences of the caller's own.  Two kernels:
 //   phaseshift_decode_kernel  planes (+ the undistortion maps) -> the projector coordinates (px, py) per pixel, NaN where masked
 //   sl_triangulate_kernel     camera points (or the pixel grid) + projector points -> points, by ftp_triangulate
-// The decode uses the partition of graycode_decode_kernel: the region's pixels are one flattened index p = ry * w + rx
-// (npix = h w < 2^31), GRAYCODE_BLOCK consecutive pixels per workgroup, thread t owns the pixels 4 t .. 4 t + 3 of its block, the
-// plane loop innermost, the taps of a pixel computed once for all planes.
+// The decode uses the partition and the front of graycode_decode_kernel (PlaneStack and plane_stack_frame of
+// graycode_kernels.hip.h): the region's pixels are one flattened index p = ry * w + rx (npix = h w < 2^31), GRAYCODE_BLOCK
+// consecutive pixels per workgroup, thread t owns the pixels 4 t .. 4 t + 3 of its block, the plane loop innermost, the taps of a
+// pixel computed once for all planes; phaseshift_coords is the body the frame calls.
 #pragma once
 #include "common.hip.h"
 #include "ftp_cloud_kernels.hip.h"
@@ -16,12 +17,8 @@ namespace ssamd {
 constexpr int SL_MAX_PERIODS = 8;              // SSAMD_SL_MAX_PERIODS of include/ssamd_structured_light.h
 
 struct PhaseShiftArgs {
-    const uint8_t *planes;          // [4 (nx + ny)][hc][wc]: I0 .. I3 of each x-period, then of each y-period
-    const float *mapx, *mapy;       // [hc][wc] undistortion maps (MAPS) or unused
+    PlaneStack stack;               // 4 (nx + ny) planes: I0 .. I3 of each x-period, then of each y-period
     double *out;                    // [h][w][2]
-    long long plane_stride;         // hc * wc < 2^31
-    long long npix;                 // h * w < 2^31
-    int hc, wc, x0, y0, w;
     int n[2];                       // periods per axis, 1 .. SL_MAX_PERIODS
     int thr2;                       // mask where a^2 + b^2 < thr2
     double T[2][SL_MAX_PERIODS];    // the periods, T[axis][0] the first
@@ -47,7 +44,8 @@ __device__ __forceinline__ void phaseshift_coords(const PhaseShiftArgs &A, const
 {
 #pragma clang fp contract(off)
     const double two_pi = 6.283185307179586476925286766559;      // 2 * np.pi, exact doubling of the double pi
-    const uint8_t *pl = A.planes;
+    const PlaneStack &S = A.stack;
+    const uint8_t *pl = S.planes;
 #pragma unroll
     for (int j = 0; j < GRAYCODE_PER_THREAD; ++j) masked[j] = false;
 #pragma unroll
@@ -59,8 +57,8 @@ __device__ __forceinline__ void phaseshift_coords(const PhaseShiftArgs &A, const
         for (int k = 0; k < A.n[axis]; ++k) {
             int I[4][GRAYCODE_PER_THREAD];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) graycode_fetch<MODE>(phaseshift_uniform(pl + i * A.plane_stride), A.wc, live, at, taps, win, I[i]);
-            pl += 4 * A.plane_stride;
+            for (int i = 0; i < 4; ++i) graycode_fetch<MODE>(phaseshift_uniform(pl + i * S.plane_stride), S.wc, live, at, taps, win, I[i]);
+            pl += 4 * S.plane_stride;
             const double T = A.T[axis][k];
 #pragma unroll
             for (int j = 0; j < GRAYCODE_PER_THREAD; ++j) {
@@ -86,31 +84,12 @@ template <bool MAPS>
 __global__ __launch_bounds__(GRAYCODE_THREADS) void phaseshift_decode_kernel(const PhaseShiftArgs A)
 {
     const long long p0 = (long long)blockIdx.x * GRAYCODE_BLOCK + GRAYCODE_PER_THREAD * (int)threadIdx.x;
-    if (p0 >= A.npix) return;                    // (no barrier in this kernel)
-    bool live[GRAYCODE_PER_THREAD];
-    uint32_t at[GRAYCODE_PER_THREAD];            // offset of the camera pixel inside a plane (and inside the maps)
-#pragma unroll
-    for (int j = 0; j < GRAYCODE_PER_THREAD; ++j) {
-        live[j] = p0 + j < A.npix;
-        const uint32_t p = live[j] ? (uint32_t)(p0 + j) : 0u;
-        const uint32_t ry = p / (uint32_t)A.w, rx = p - ry * (uint32_t)A.w;
-        at[j] = (uint32_t)(A.y0 + (int)ry) * (uint32_t)A.wc + (uint32_t)(A.x0 + (int)rx);
-    }
-    bool masked[GRAYCODE_PER_THREAD];
+    if (p0 >= A.stack.npix) return;              // (no barrier in this kernel)
+    bool live[GRAYCODE_PER_THREAD], masked[GRAYCODE_PER_THREAD];
     double coord[2][GRAYCODE_PER_THREAD];
-    if (MAPS) {
-        GrayTaps taps[GRAYCODE_PER_THREAD];
-#pragma unroll
-        for (int j = 0; j < GRAYCODE_PER_THREAD; ++j)      // (a pixel past the end: no taps)
-            taps[j] = graycode_taps(live[j] ? A.mapx[at[j]] : __builtin_nanf(""), live[j] ? A.mapy[at[j]] : 0.f, A.hc, A.wc);
-        const GrayWindow win = graycode_window(taps, live, A.wc, A.plane_stride);
-        if (win.ok) phaseshift_coords<GRAY_WINDOW>(A, live, at, taps, &win, coord, masked);
-        else phaseshift_coords<GRAY_TAPS>(A, live, at, taps, nullptr, coord, masked);
-    } else if (live[GRAYCODE_PER_THREAD - 1] && at[GRAYCODE_PER_THREAD - 1] == at[0] + (GRAYCODE_PER_THREAD - 1)) {
-        phaseshift_coords<GRAY_ROW4>(A, live, at, nullptr, nullptr, coord, masked);      // all alive and consecutive bytes of a plane
-    } else {
-        phaseshift_coords<GRAY_BYTES>(A, live, at, nullptr, nullptr, coord, masked);
-    }
+    plane_stack_frame<MAPS>(A.stack, p0, live, [&](auto mode, const uint32_t (&at)[GRAYCODE_PER_THREAD], const GrayTaps *taps, const GrayWindow *win) {
+        phaseshift_coords<decltype(mode)::value>(A, live, at, taps, win, coord, masked);
+    });
     const double nan = __longlong_as_double(0x7ff8000000000000ll);
     double2 *const o = reinterpret_cast<double2 *>(A.out) + p0;
 #pragma unroll

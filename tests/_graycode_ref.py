@@ -285,3 +285,39 @@ def scene(seed, res1, res2, noise=0, holes=0.1):
     if noise:
         out = np.clip(out.astype(np.int64) + rng.integers(-noise, noise + 1, out.shape), 0, 255).astype(np.uint8)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ the front of the decode kernels
+GRAY_ROW4, GRAY_BYTES, GRAY_TAPS, GRAY_WINDOW = 0, 1, 2, 3      # the modes of graycode_kernels.hip.h
+WINDOW_CONDITIONS = ("dead", "outside", "columns", "rows", "end")
+
+
+def front(hc, wc, box, maps=None):
+    """plane_stack_frame of graycode_kernels.hip.h restated: for the region `box` = (x0, y0, w, h) of hc x wc planes, per thread of
+    four consecutive region pixels that owns a pixel -> (mode int [threads], {condition: bool [threads]}).  The conditions, under
+    maps only, are those of graycode_window, each True where it FAILS (several may): a `dead` pixel (past the region's end), a tap
+    of a living pixel `outside` the image, a column spread over 6, a row spread over 1, the third row's 8 bytes ending outside
+    the plane (`end`); the mode is GRAY_WINDOW where none fails and GRAY_TAPS otherwise.  A pixel without an interior cell counts
+    as cell (0, 0) in the spreads, as in the kernel."""
+    x0, y0, w, h = box
+    npix = h * w
+    p = 4 * np.arange((npix + 3) // 4, dtype=np.int64)[:, None] + np.arange(4)
+    live = p < npix
+    q = np.where(live, p, 0)
+    at = (y0 + q // max(w, 1)) * wc + (x0 + q % max(w, 1))
+    if maps is None:
+        row4 = live[:, 3] & (at[:, 3] == at[:, 0] + 3)
+        return np.where(row4, GRAY_ROW4, GRAY_BYTES), {}
+    mx = np.where(live, np.asarray(maps[0], np.float32).ravel()[at], np.float32(np.nan))
+    my = np.where(live, np.asarray(maps[1], np.float32).ravel()[at], np.float32(0))
+    with np.errstate(invalid="ignore"):
+        finite = (np.abs(mx) < 2.0 ** 26) & (np.abs(my) < 2.0 ** 26)
+        cx = np.rint(np.where(finite, mx, 0).astype(np.float64) * 32.0).astype(np.int64) >> 5      # llrint: half to even
+        cy = np.rint(np.where(finite, my, 0).astype(np.float64) * 32.0).astype(np.int64) >> 5
+    interior = finite & (cx >= 0) & (cx + 1 < wc) & (cy >= 0) & (cy + 1 < hc)
+    cx, cy = np.where(interior, cx, 0), np.where(interior, cy, 0)
+    lo_x, lo_y = cx.min(axis=1), cy.min(axis=1)
+    fails = {"dead": ~live.all(axis=1), "outside": (live & ~interior).any(axis=1), "columns": cx.max(axis=1) - lo_x > 6,
+             "rows": cy.max(axis=1) - lo_y > 1, "end": (lo_y + 2) * wc + lo_x + 8 > hc * wc}
+    window = ~np.logical_or.reduce([fails[c] for c in WINDOW_CONDITIONS])
+    return np.where(window, GRAY_WINDOW, GRAY_TAPS), fails

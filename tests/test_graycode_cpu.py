@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import _graycode_ref as G
+import _plane_stack as X
 from test_native_signatures_cpu import SCALARS, _is_pointer_class, _prototypes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -127,9 +128,7 @@ def test_abi_argument_errors_need_no_device():
                out=out.ctypes.data):
         return lib.ssamd_graycode_decode(planes, n, hc, wc, mx, my, x0, y0, h, w, ncol, nrow, pw, ph, thr, out, None, -1)
 
-    bad = [dict(planes=None), dict(out=None), dict(h=-1), dict(x0=-1), dict(x0=1), dict(y0=1), dict(w=9), dict(n=12), dict(ncol=17, nrow=-10),
-           dict(nrow=-1, ncol=8), dict(thr=-1), dict(thr=257), dict(pw=0), dict(ph=65537), dict(mx=maps.ctypes.data), dict(my=maps.ctypes.data),
-           dict(hc=1 << 16, wc=1 << 15), dict(hc=-4)]
+    bad = X.gray_bad(maps)
     for kw in bad:
         assert decode(**kw) == _native.EINVAL, kw
         assert lib.ssamd_last_error()

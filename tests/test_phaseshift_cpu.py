@@ -11,6 +11,7 @@ import pytest
 
 import _ftp_cloud_ref as C
 import _graycode_ref as G
+import _plane_stack as X
 import _phaseshift_ref as P
 from test_native_signatures_cpu import SCALARS, _is_pointer_class, _prototypes
 
@@ -75,11 +76,7 @@ def test_abi_argument_errors_need_no_device():
                 pw, ph, thr2, out)
         return lib.ssamd_phaseshift_decode_device(*args, None) if device else lib.ssamd_phaseshift_decode(*args, -1)
 
-    bad = [dict(planes=None), dict(out=None), dict(tx=None), dict(ty=None), dict(h=-1), dict(w=-1), dict(x0=-1), dict(y0=-1), dict(x0=1), dict(y0=1), dict(w=9),
-           dict(h=5), dict(n=16), dict(n=24), dict(nx=0, ny=5), dict(nx=9, ny=-4), dict(ny=0, nx=5), dict(ny=9, nx=-4), dict(thr2=-1), dict(pw=0), dict(ph=0),
-           dict(pw=65537), dict(ph=65537), dict(mx=maps.ctypes.data), dict(my=maps.ctypes.data), dict(hc=1 << 16, wc=1 << 15), dict(hc=-4), dict(wc=-8),
-           dict(tx=np.array([64.0, 0.0, 5.0])), dict(tx=np.array([64.0, -16.0, 5.0])), dict(tx=np.array([np.inf, 16.0, 5.0])),
-           dict(ty=np.array([32.0, np.nan])), dict(ty=np.array([-0.0, 8.0]))]
+    bad = X.phase_bad(maps)
     for kw in bad:
         for device in (False, True):
             assert decode(device=device, **kw) == _native.EINVAL, (kw, device)
