@@ -34,14 +34,6 @@ struct AswAltArgs {
     float kC;                    // -log2(e)/gammaC
 };
 
-// support weight of one tap, the arithmetic of asw_aggregate_kernel's weight build
-__device__ __forceinline__ float asw_alt_weight(const PixRec tap, const PixRec cen, float prox, float kC)
-{
-    const float dL = tap.L - cen.L, da = tap.a - cen.a, db = tap.b - cen.b;
-    const float dist = __builtin_amdgcn_sqrtf(fmaf(db, db, fmaf(da, da, dL * dL)));
-    return asw_weight_finish(dist, kC, prox);
-}
-
 __device__ __forceinline__ float asw_alt_wave_sum(float v)
 {
 #pragma unroll
@@ -70,15 +62,15 @@ __device__ __forceinline__ u64 asw_alt_eval(const AswAltArgs &A, int y, int x, i
         if ((unsigned)yy < (unsigned)H && (unsigned)xl < (unsigned)W) {
             const PixRec tl = A.recL[(size_t)yy * W + xl];
             const float pr = A.prox[t];
-            const float wl = asw_alt_weight(tl, cl, pr, A.kC);
+            const float wl = asw_support_weight(tl, cl, A.kC, pr);
             const PixRec *const rrow = A.recR + (size_t)yy * W;
 #pragma unroll
             for (int c = 0; c < ASW_ALT_JC; ++c) {
                 const int xrj = xl - d0 - min(c, cnt - 1);
                 if ((unsigned)xrj < (unsigned)W) {
                     const PixRec tr = rrow[xrj];
-                    const float w = wl * asw_alt_weight(tr, cr[c], pr, A.kC);
-                    const float e = (float)min(__builtin_amdgcn_sad_u8(tl.bgrx, tr.bgrx, 0u), 40u);
+                    const float w = wl * asw_support_weight(tr, cr[c], A.kC, pr);
+                    const float e = (float)asw_tad(tl.bgrx, tr.bgrx);
                     n[c] = fmaf(w, e, n[c]);
                     s[c] = fmaf(w, ASW_TAD_CAP - e, s[c]);
                 }

@@ -179,12 +179,8 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, RX == 8 ? 3 : 4) void asw_aggregat
             while (sp < nsp) {
                 const uint32_t lp = bgrLc[ul];
                 const uint32_t *const rp = bgrRc + (ul + (Dc - 1) - 8 * sp);   // R[u-d] for d = dlo + 8*sp
-                uint32_t lo = 0, hi = 0;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    lo |= min(__builtin_amdgcn_sad_u8(lp, rp[-k], 0u), 40u) << (8 * k);
-                    hi |= min(__builtin_amdgcn_sad_u8(lp, rp[-4 - k], 0u), 40u) << (8 * k);
-                }
+                uint32_t lo, hi;
+                asw_tad8(lp, rp, lo, hi);
                 *reinterpret_cast<uint32_t *>(eT + asw_e_offset<RX>(ul, 2 * sp, Se, emask)) = lo;
                 if (2 * sp + 1 < g.DG) *reinterpret_cast<uint32_t *>(eT + asw_e_offset<RX>(ul, 2 * sp + 1, Se, emask)) = hi;
                 ul += e_r; sp += e_q;
@@ -233,60 +229,35 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, RX == 8 ? 3 : 4) void asw_aggregat
                     const uint32_t cmask = cen.w != 0.f ? 0xffffffffu : 0u;
                     // batches of ASW_WB independent evaluations: all LDS reads first, then the dependent
                     // chains (sub, fma, v_sqrt, v_exp, mul) side by side -- a single chain is ~150 cycles of
-                    // latency, and during this phase every wave of the group is in the same loop.  Whole
-                    // batches walk running pointers (staged pixels, proximity row, output column); only the
-                    // last, partial batch of a segment pays for clamped indices.
+                    // latency, and during this phase every wave of the group is in the same loop.  ONE batch body:
+                    // entry u is tap at(u) past the column that sp, pp, wp and col stand for.  Whole batches walk
+                    // running pointers (staged pixels, proximity row, output column) and take the taps 0, 1, ..;
+                    // only the last, partial batch of a segment pays for indices clamped to the segment's end, where
+                    // the clamped tap is simply rewritten (straight-line batches of 1 - 3 instead, as the phase-shifted
+                    // kernel has them, measured 1.6 - 2.5 % slower here: profiles/fp32_steps_fold.txt).
+                    auto batch = [&](const float4 *sp, const float *pp, float *wp, int col, auto at) {
+                        float4 tp[ASW_WB];
+                        float pr[ASW_WB], wv[ASW_WB];
+#pragma unroll
+                        for (int u = 0; u < ASW_WB; ++u) { tp[u] = sp[at(u)]; pr[u] = pp[at(u)]; }
+#pragma unroll
+                        for (int u = 0; u < ASW_WB; ++u) wv[u] = asw_lab_dist2(tp[u], cen);
+                        asw_support_weights(wv, A.kC, pr);
+#pragma unroll
+                        for (int u = 0; u < ASW_WB; ++u) {
+                            const uint32_t m = (unsigned)(col + at(u)) < (unsigned)W ? cmask : 0u;
+                            wp[at(u) * stride] = __uint_as_float(__float_as_uint(wv[u]) & m);
+                        }
+                    };
                     int j = jc + sgm * g.wlen;
                     const float4 *sp = seg + j;
                     const float *pp = prow + j;
                     float *wp = wout + j * stride;
                     int col = col0 + j;
                     const int stride4 = ASW_WB * stride;
-                    for (; j + ASW_WB <= j1; j += ASW_WB, sp += ASW_WB, pp += ASW_WB, wp += stride4, col += ASW_WB) {
-                        float4 tp[ASW_WB];
-                        float pr[ASW_WB], wv[ASW_WB];
-#pragma unroll
-                        for (int u = 0; u < ASW_WB; ++u) { tp[u] = sp[u]; pr[u] = pp[u]; }
-#pragma unroll
-                        for (int u = 0; u < ASW_WB; ++u) {
-                            const float dL = tp[u].x - cen.x, da = tp[u].y - cen.y, db = tp[u].z - cen.z;
-                            wv[u] = fmaf(db, db, fmaf(da, da, dL * dL));
-                        }
-#pragma unroll
-                        for (int u = 0; u < ASW_WB; ++u) wv[u] = __builtin_amdgcn_sqrtf(wv[u]);
-#pragma unroll
-                        for (int u = 0; u < ASW_WB; ++u) wv[u] = asw_weight_finish(wv[u], A.kC, pr[u]);
-#pragma unroll
-                        for (int u = 0; u < ASW_WB; ++u) {
-                            const uint32_t m = (unsigned)(col + u) < (unsigned)W ? cmask : 0u;
-                            wp[u * stride] = __uint_as_float(__float_as_uint(wv[u]) & m);
-                        }
-                    }
-                    if (j < j1) {
-                        float4 tp[ASW_WB];
-                        float pr[ASW_WB], wv[ASW_WB];
-#pragma unroll
-                        for (int u = 0; u < ASW_WB; ++u) {
-                            const int jj = min(j + u, j1 - 1);
-                            tp[u] = seg[jj];
-                            pr[u] = prow[jj];
-                        }
-#pragma unroll
-                        for (int u = 0; u < ASW_WB; ++u) {
-                            const float dL = tp[u].x - cen.x, da = tp[u].y - cen.y, db = tp[u].z - cen.z;
-                            wv[u] = fmaf(db, db, fmaf(da, da, dL * dL));
-                        }
-#pragma unroll
-                        for (int u = 0; u < ASW_WB; ++u) wv[u] = __builtin_amdgcn_sqrtf(wv[u]);
-#pragma unroll
-                        for (int u = 0; u < ASW_WB; ++u) wv[u] = asw_weight_finish(wv[u], A.kC, pr[u]);
-#pragma unroll
-                        for (int u = 0; u < ASW_WB; ++u) {  // past the segment end the clamped tap is simply rewritten
-                            const int jj = min(j + u, j1 - 1);
-                            const uint32_t m = (unsigned)(col0 + jj) < (unsigned)W ? cmask : 0u;
-                            wout[jj * stride] = __uint_as_float(__float_as_uint(wv[u]) & m);
-                        }
-                    }
+                    for (; j + ASW_WB <= j1; j += ASW_WB, sp += ASW_WB, pp += ASW_WB, wp += stride4, col += ASW_WB)
+                        batch(sp, pp, wp, col, [](int u) { return u; });
+                    if (j < j1) batch(seg, prow, wout, col0, [&](int u) { return min(j + u, j1 - 1); });
                 }
             }
             __syncthreads();   // e tile and this chunk of wL, wR ready; every thread is done with the previous chunk

@@ -172,12 +172,8 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(
         while (t < t_hi) {
             const uint32_t lp = bgrLc[ul];
             const uint32_t *const rp = bgrRc + (ul + (Dc - 1) - 8 * sp);   // R[u-d] for d = dlo + 8*sp
-            uint32_t lo = 0, hi = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                lo |= min(__builtin_amdgcn_sad_u8(lp, rp[-k], 0u), 40u) << (8 * k);
-                hi |= min(__builtin_amdgcn_sad_u8(lp, rp[-4 - k], 0u), 40u) << (8 * k);
-            }
+            uint32_t lo, hi;
+            asw_tad8(lp, rp, lo, hi);
             uint32_t *const dst = reinterpret_cast<uint32_t *>(eT + ul * Se) + 2 * sp;
             dst[0] = lo;
             if (2 * sp + 1 < g.DG) dst[1] = hi;
@@ -230,13 +226,9 @@ __global__ __launch_bounds__(ASW_MAX_THREADS, 3) void asw_aggregate_pipe_kernel(
 #pragma unroll
             for (int u = 0; u < N; ++u) {
                 asm volatile("" ::"v"(tp[u].w));     // keeps the read a ds_read_b128 (4 LDS cycles; the 12-byte form takes 8)
-                const float dL = tp[u].x - cen.x, da = tp[u].y - cen.y, db = tp[u].z - cen.z;
-                wv[u] = fmaf(db, db, fmaf(da, da, dL * dL));
+                wv[u] = asw_lab_dist2(tp[u], cen);
             }
-#pragma unroll
-            for (int u = 0; u < N; ++u) wv[u] = __builtin_amdgcn_sqrtf(wv[u]);
-#pragma unroll
-            for (int u = 0; u < N; ++u) wv[u] = asw_weight_finish(wv[u], A.kC, pr[u]);
+            asw_support_weights(wv, A.kC, pr);
 #pragma unroll
             for (int u = 0; u < N; ++u) wp[u * stride] = wv[u];
         };

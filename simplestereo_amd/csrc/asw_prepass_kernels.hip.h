@@ -32,11 +32,7 @@ __device__ __forceinline__ void asw_tad_tile(const void *__restrict__ srcL, cons
     auto pixel = [&](const void *src, int col) -> uint32_t {
         const size_t q = (size_t)r * W + col;
         if constexpr (BYTES) {
-            typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
-            const uint8_t *const b = reinterpret_cast<const uint8_t *>(src) + 3 * q;
-            // (the 4-byte read of the image's last pixel would run one byte past the buffer)
-            return (long long)q + 1 < npix_total ? (*reinterpret_cast<const u32_unaligned *>(b) & 0xffffffu)
-                                                 : ((uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16));
+            return load_bgr(reinterpret_cast<const uint8_t *>(src), (long long)q, npix_total);
         } else {
             return reinterpret_cast<const PixRec *>(src)[q].bgrx;
         }
@@ -62,7 +58,7 @@ __device__ __forceinline__ void asw_tad_tile(const void *__restrict__ srcL, cons
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const uint32_t rv = q < nv && d0 + q < Dc ? rp[-q] : 0x80000000u;
-                if (!(rv >> 31)) v |= min(__builtin_amdgcn_sad_u8(lp, rv, 0u), 40u) << (8 * q);
+                if (!(rv >> 31)) v |= asw_tad(lp, rv) << (8 * q);
             }
         }
         return v;
@@ -94,8 +90,8 @@ __global__ __launch_bounds__(256) void asw_tad_volume_kernel(const PixRec *__res
 }
 
 // K0 + K0e in ONE launch (round 5): the first `lab_blocks` workgroups convert the pixels of the rows [erow0, erow0 + erows) of both
-// images into records (bgr2lab_records_pair_kernel's job, same code), the others each build one tile of the volume from the
-// images' bytes.  The two jobs do not depend on each other, so a small-frame call is two dependent launches instead of three
+// images into records (bgr2lab_records_pair_kernel's job by the same function, lab_records_pair), the others each build one tile of
+// the volume from the images' bytes.  The two jobs do not depend on each other, so a small-frame call is two dependent launches instead of three
 // (a launch-to-launch dependency costs more than either kernel at Tsukuba size).  bgrL / bgrR: the sub-image's row 0.
 struct AswPrepassArgs {
     const uint8_t *bgrL, *bgrR;
@@ -112,24 +108,8 @@ __global__ __launch_bounds__(256) void asw_prepass_kernel(const AswPrepassArgs P
         SSAMD_LAB_TABLES_IN_LDS(T)
         const long long np = (long long)P.erows * P.W, first = (long long)P.erow0 * P.W;
         const uint8_t *const bl = P.bgrL + 3 * first, *const br = P.bgrR + 3 * first;
-        PixRec *const rl = P.recL + first, *const rr = P.recR + first;
-        typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
-        for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < 2 * np; q += (long long)P.lab_blocks * blockDim.x) {
-            const bool right = q >= np;
-            const long long p = right ? q - np : q;
-            const uint8_t *const bgr = right ? br : bl;
-            uint32_t B, G, R;
-            if (p + 1 < np) {
-                const uint32_t v = *reinterpret_cast<const u32_unaligned *>(bgr + 3 * p);
-                B = v & 0xff; G = (v >> 8) & 0xff; R = (v >> 16) & 0xff;
-            } else {
-                B = bgr[3 * p]; G = bgr[3 * p + 1]; R = bgr[3 * p + 2];
-            }
-            PixRec o;
-            bgr_to_lab(B, G, R, o.L, o.a, o.b, T);
-            o.bgrx = B | (G << 8) | (R << 16);
-            (right ? rr : rl)[p] = o;
-        }
+        lab_records_pair(P.recL + first, P.recR + first, np, P.lab_blocks, T,
+                         [&](bool right, long long p) { return load_bgr(right ? br : bl, p, np); });
         return;
     }
     const int b = (int)blockIdx.x - P.lab_blocks, bx = b % P.ex, by = (b / P.ex) % P.ey, bz = b / (P.ex * P.ey);

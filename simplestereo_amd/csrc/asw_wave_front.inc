@@ -91,9 +91,7 @@
     // (no lane guards: reads up to 127 entries past a part's end stay inside the wave's LDS slice and the weight rows
     // are padded to whole rounds, so the surplus lanes of the last round write weights nobody reads)
     auto weight = [&](const float4 &ce, const float4 &tp, float pj) {
-        const float dL = tp.x - ce.x, da = tp.y - ce.y, db = tp.z - ce.z;
-        const float dist = __builtin_amdgcn_sqrtf(fmaf(db, db, fmaf(da, da, dL * dL)));
-        return asw_weight_finish(dist, A.kC, pj);
+        return asw_support_weight(tp, ce, A.kC, pj);
     };
     // Two tap columns (j, j + 1) per build: a centre is read once for both, and the wave pays the LDS round trip of a
     // build once per two aggregation steps.  Weight row q = column parity, at wS + q * wrow.

@@ -28,6 +28,7 @@
 // same LDS read volume per tap (three 16-byte reads per 32 multiply-add pairs).
 #pragma once
 #include "common.hip.h"
+#include "lab_kernels.hip.h"      // load_bgr
 
 namespace ssamd {
 
@@ -437,8 +438,7 @@ __global__ __launch_bounds__(256) void bgr_pack_kernel(const uint8_t *__restrict
 {
     long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long long stride = (long long)gridDim.x * blockDim.x;
-    for (; p < npix; p += stride)
-        out[p] = (uint32_t)bgr[3 * p] | ((uint32_t)bgr[3 * p + 1] << 8) | ((uint32_t)bgr[3 * p + 2] << 16);
+    for (; p < npix; p += stride) out[p] = load_bgr(bgr, p, npix);
 }
 
 }  // namespace ssamd

@@ -67,34 +67,51 @@ __device__ __forceinline__ void bgr_to_lab(uint32_t B, uint32_t G, uint32_t R, f
     b = (float)b64;
 }
 
-// One thread per pixel; 4 consecutive pixels share 12 contiguous bytes but a 3-byte-per-lane read is still fully
-// coalesced at the wave level (192 B/wave): one unaligned 4-byte read instead of three byte reads (the 4th byte is the
-// next pixel's).
+// The pixel front of the matchers, each step written once.
+// Pixel p of a uint8 [npix][3] image as B | G << 8 | R << 16.  4 consecutive pixels share 12 contiguous bytes but a 3-byte-per-lane
+// read is still fully coalesced at the wave level (192 B/wave): one unaligned 4-byte read instead of three byte reads (the 4th byte
+// is the next pixel's); byte reads for the last pixel, whose 4-byte read would run one byte past the buffer.
+__device__ __forceinline__ uint32_t load_bgr(const uint8_t *__restrict__ img, long long p, long long npix)
+{
+    typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
+    const uint8_t *const b = img + 3 * p;
+    return p + 1 < npix ? (*reinterpret_cast<const u32_unaligned *>(b) & 0xffffffu)
+                        : ((uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16));
+}
+
+// packed pixel -> record: its Lab values and the bytes themselves
+__device__ __forceinline__ PixRec lab_record(uint32_t bgr, const LabTables &T)
+{
+    PixRec o;
+    bgr_to_lab(bgr & 0xff, (bgr >> 8) & 0xff, (bgr >> 16) & 0xff, o.L, o.a, o.b, T);
+    o.bgrx = bgr;
+    return o;
+}
+
+// The records of an image pair by the `blocks` workgroups of one launch: item q of 2 * npix -> (right image?, pixel p), whose
+// packed pixel is pixel(right, p).
 // Both images of a pair in ONE launch (round 3: a 1080p image is a 20 us kernel, two of them plus the gap between two
 // dependent launches were a third of the pre-pass; at Tsukuba size the launch is most of it).
+// (The two remap kernels of rig_kernels.hip.h walk their pair with a loop of their own: through this function their device
+// code changed, profiles/fp32_steps_fold.txt.)
+template <class F>
+__device__ __forceinline__ void lab_records_pair(PixRec *__restrict__ recL, PixRec *__restrict__ recR, long long npix, unsigned blocks,
+                                                 const LabTables &T, F pixel)
+{
+    long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long stride = (long long)blocks * blockDim.x;
+    for (; q < 2 * npix; q += stride) {
+        const bool right = q >= npix;
+        const long long p = right ? q - npix : q;
+        (right ? recR : recL)[p] = lab_record(pixel(right, p), T);
+    }
+}
+
 __global__ __launch_bounds__(256) void bgr2lab_records_pair_kernel(const uint8_t *__restrict__ bgrL, const uint8_t *__restrict__ bgrR,
                                                                    PixRec *__restrict__ recL, PixRec *__restrict__ recR, long long npix)
 {
     SSAMD_LAB_TABLES_IN_LDS(T)
-    long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
-    for (; q < 2 * npix; q += stride) {
-        const bool right = q >= npix;
-        const long long p = right ? q - npix : q;
-        const uint8_t *const bgr = right ? bgrR : bgrL;
-        uint32_t B, G, R;
-        if (p + 1 < npix) {
-            const uint32_t v = *reinterpret_cast<const u32_unaligned *>(bgr + 3 * p);
-            B = v & 0xff; G = (v >> 8) & 0xff; R = (v >> 16) & 0xff;
-        } else {
-            B = bgr[3 * p]; G = bgr[3 * p + 1]; R = bgr[3 * p + 2];
-        }
-        PixRec o;
-        bgr_to_lab(B, G, R, o.L, o.a, o.b, T);
-        o.bgrx = B | (G << 8) | (R << 16);
-        (right ? recR : recL)[p] = o;
-    }
+    lab_records_pair(recL, recR, npix, gridDim.x, T, [&](bool right, long long p) { return load_bgr(right ? bgrR : bgrL, p, npix); });
 }
 
 // debug/verification: plain float32 Lab image
@@ -105,11 +122,10 @@ __global__ __launch_bounds__(256) void bgr2lab_f32_kernel(const uint8_t *__restr
     long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (; p < npix; p += stride) {
-        float L, a, b;
-        bgr_to_lab(bgr[3 * p], bgr[3 * p + 1], bgr[3 * p + 2], L, a, b, T);
-        lab[3 * p] = L;
-        lab[3 * p + 1] = a;
-        lab[3 * p + 2] = b;
+        const PixRec o = lab_record(load_bgr(bgr, p, npix), T);
+        lab[3 * p] = o.L;
+        lab[3 * p + 1] = o.a;
+        lab[3 * p + 2] = o.b;
     }
 }
 

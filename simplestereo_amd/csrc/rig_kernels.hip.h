@@ -112,10 +112,7 @@ __global__ __launch_bounds__(256) void remap_lab_records_pair_kernel(const Remap
         const long long p = pix0 + (right ? q - npix : q);
         const uint32_t v = remap_pixel(right ? S.src2 : S.src1, S.Hs, S.Ws, src_bytes, (right ? S.mapx2 : S.mapx1)[p],
                                        (right ? S.mapy2 : S.mapy1)[p], S.nearest);
-        PixRec o;
-        bgr_to_lab(v & 0xff, (v >> 8) & 0xff, (v >> 16) & 0xff, o.L, o.a, o.b, T);
-        o.bgrx = v;
-        (right ? recR : recL)[p] = o;
+        (right ? recR : recL)[p] = lab_record(v, T);
     }
 }
 

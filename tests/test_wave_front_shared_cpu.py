@@ -7,8 +7,10 @@ import re
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "simplestereo_amd", "csrc")
 SHARED = ["asw_wave_front.inc", "asw_wave_row.inc"]
 WAVE_HEADERS = ["asw_wave_kernel.hip.h", "asw_wave6_kernel.hip.h"]
-# what only the shared text does: LDS-DMA of the e tile, the support weight, the tap offsets of the merged build
-SHARED_ONLY = ["__builtin_amdgcn_global_load_lds", "asw_weight_finish(", "__builtin_amdgcn_sqrtf", "tapoff["]
+# what only the shared text does: LDS-DMA of the e tile, the support weight (common.hip.h's helper: the square root and
+# asw_weight_finish behind it are in neither the kernels nor the shared text, tests/test_fp32_steps_shared_cpu.py), the tap offsets
+# of the merged build
+SHARED_ONLY = ["__builtin_amdgcn_global_load_lds", "asw_support_weight(", "tapoff["]
 # names a preprocessor conditional may test: the ones the build itself defines (simplestereo_amd/build.py, the translation units,
 # the compiler).  A compile-time variant of a kernel is a source tree of its own (tools/ab_tree.py), not an #ifdef.
 CONDITIONAL_NAMES = {"SSAMD_PIPE_INSTANCE", "SSAMD_WAVE6_INSTANCE", "GM_HOST_TABLES", "__HIPCC__", "__HIP_DEVICE_COMPILE__"}
