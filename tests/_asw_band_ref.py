@@ -24,6 +24,7 @@ changes form) is not measured either; a pair enters a measure only if all four i
 import numpy as np
 
 import _tie_inputs as T
+from _asw_forms import FORMS        # noqa: F401  (the case matrix names its forms)
 
 NONE32 = 0xFFFFFFFF                    # the dump's word where a candidate does not exist
 HIGH = 0xC0000000 - 0x41A00000         # images at or above this hold 40 - cost (EXACT_KEY_HIGH)
@@ -171,22 +172,7 @@ def emulate32(L, R, p):
 
 
 # ---- the case matrix ----------------------------------------------------------------------------------------------------------
-# Kernel forms: options that force them and what ssamd_asw_kernel_form / ssamd_asw_geometry must then say.  None of the options
-# is SSAMD_ASW_COST_KEYS's business: it forces no form.
-FORMS = {
-    "planner": (dict(SSAMD_AUTOTUNE="0"), dict()),
-    "wave4": (dict(SSAMD_ASW_WAVE="1", SSAMD_ASW_WAVE_RX="4"), dict(wave_kernel=4)),
-    "wave8": (dict(SSAMD_ASW_WAVE="1", SSAMD_ASW_WAVE_RX="8"), dict(wave_kernel=8)),
-    "wave6": (dict(SSAMD_ASW_WAVE="1", SSAMD_ASW_WAVE_RX="4"), dict(wave_kernel=4, chunk_d=18)),
-    "wave4x5": (dict(SSAMD_ASW_WAVE="1", SSAMD_ASW_WAVE_RX="4", SSAMD_ASW_WAVE_RD="4"), dict(wave_kernel=4, chunk_d=20)),
-    "pipe": (dict(SSAMD_ASW_WAVE="0", SSAMD_AUTOTUNE="0"), dict(phase_shifted=1, wave_kernel=0)),
-    "pipe_evol0": (dict(SSAMD_ASW_WAVE="0", SSAMD_ASW_EVOL="0"), dict(phase_shifted=1, wave_kernel=0)),
-    "pipe8": (dict(SSAMD_ASW_WAVE="0", SSAMD_ASW_PIPE="8"), dict(phase_shifted=1, chunk_columns=8, wave_kernel=0)),
-    "pipe8_evol0": (dict(SSAMD_ASW_WAVE="0", SSAMD_ASW_PIPE="8", SSAMD_ASW_EVOL="0"), dict(phase_shifted=1, chunk_columns=8, wave_kernel=0)),
-    "workgroup": (dict(SSAMD_ASW_WAVE="0", SSAMD_ASW_PIPE="0"), dict(phase_shifted=0, wave_kernel=0)),
-    "chunks": (dict(SSAMD_AUTOTUNE="0"), dict(n_chunks=lambda n: n > 1)),
-}
-
+# Kernel forms: the catalogue of tests/_asw_forms.py, by name.
 # name: generator (of _tie_inputs), shape, seed, params (minDisparity 0), forms, differential measure or per candidate only
 CASES = {}
 

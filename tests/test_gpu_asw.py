@@ -9,7 +9,9 @@ import os
 
 import numpy as np
 import pytest
-from simplestereo_amd import _native      # noqa: E402  (tuning options: _native.set_option)
+from simplestereo_amd import _native
+
+import _asw_forms as F
 
 pytestmark = pytest.mark.gpu
 
@@ -58,19 +60,12 @@ def test_asw_vs_reference_golden(cid, ss, golden_cases, golden_inputs):
 ])
 def test_asw_raw_costs_vs_oracle(shape, params, ss, tsukuba):
     """raw aggregated costs (fp32 kernels vs fp64 oracle), including which entries exist"""
-    import ctypes
     from oracle import oracle
-    from simplestereo_amd import _native
     from simplestereo_amd.synth import make_pair
     H, W = shape
     a, b, _ = make_pair(H, W, params["maxDisparity"], seed=H + W)
     _, cref = oracle.asw(a, b, return_costs=True, **params)
-    nD = params["maxDisparity"] - params["minDisparity"] + 1
-    c = np.empty((H, W, nD), np.float32)
-    _native.check(_native.lib().ssamd_asw_costs(a.ctypes.data, b.ctypes.data, H, W, params["winSize"],
-                                                params["maxDisparity"], params["minDisparity"],
-                                                float(params["gammaC"]), float(params["gammaP"]),
-                                                c.ctypes.data, -1))
+    c = F.cost_dump(a, b, params)
     assert np.array_equal(np.isnan(c), np.isnan(cref))
     ok = ~np.isnan(cref)
     err = np.abs(c[ok] - cref[ok]) / np.maximum(1.0, np.abs(cref[ok]))
@@ -147,31 +142,43 @@ def test_asw_degenerate_ranges(ss, golden_inputs):
     assert np.array_equal(ss.passive.StereoASW(**p).compute(flat, flat), oracle.asw(flat, flat, **p))
 
 
-@pytest.mark.parametrize("geom", ["6,5,8", "10,9,16", "3,9,8", "12,3,8", "12,5,0,4", "7,9,8,4", "20,3,4,4", "5,10,12,4"])
+SYNTH = (128, 96)        # W, H of the golden input synth_96x128
+GEOMS = ["6,5,8", "10,9,16", "3,9,8", "12,3,8", "12,5,0,4", "7,9,8,4", "20,3,4,4", "5,10,12,4"]
+
+
+def _geometry_rows(geom):
+    """the forced tile; the same tile without the second e tile (row-start barrier kept); and with the XOR-swizzled e rows only"""
+    p = dict(winSize=21, maxDisparity=int(geom.split(",")[1]) * 4 - 1, minDisparity=0)      # geom = XG,DG[,JC[,RX]]: 4-column register tiles as well
+    return [(F.workgroup_tile(geom, **extra),) + SYNTH + (p,)
+            for extra in ({}, dict(SSAMD_ASW_NO_E2="1"), dict(SSAMD_ASW_NO_E2="1", SSAMD_ASW_XOR_ONLY="1"))]
+
+
+@pytest.mark.parametrize("geom", GEOMS)
 def test_asw_forced_geometries_and_chunked_staging_agree(geom, ss, golden_inputs):
     """every launch geometry (tile shape, tap-column chunking) computes the same sums in the same order:
     forced shapes via the SSAMD_ASW_GEOM tuning hook must reproduce the default result bit for bit"""
     a, b = golden_inputs("synth_96x128")
-    maxd = int(geom.split(",")[1]) * 4 - 1        # geom = XG,DG[,JC[,RX]]: 4-column register tiles as well
-    m = ss.passive.StereoASW(winSize=21, maxDisparity=maxd, minDisparity=0, consistent=True)
+    rows = _geometry_rows(geom)
+    m = ss.passive.StereoASW(consistent=True, **rows[0][3])
     want = m.compute(a, b)
-    _native.set_option("SSAMD_ASW_GEOM", geom)
-    try:
-        got = m.compute(a, b)
-        # the same tile without the second e tile (row-start barrier kept) and with the XOR-swizzled e rows only
-        _native.set_option("SSAMD_ASW_NO_E2", "1")
-        got_one_e = m.compute(a, b)
-        _native.set_option("SSAMD_ASW_XOR_ONLY", "1")
-        got_xor = m.compute(a, b)
-    finally:
-        for k in ("SSAMD_ASW_GEOM", "SSAMD_ASW_NO_E2", "SSAMD_ASW_XOR_ONLY"):
-            _native.set_option(k, None)
-    assert np.array_equal(got, want)
-    assert np.array_equal(got_one_e, want) and np.array_equal(got_xor, want)
+    for row in rows:
+        with F.forced(*row):
+            assert np.array_equal(m.compute(a, b), want), row[0][0]
 
 
-@pytest.mark.parametrize("geom,win", [("6,5,8", 21), ("10,9,16", 35), ("3,9,8", 17), ("12,3,8", 35), ("15,13,16", 35), ("9,17,8", 33),
-                                      ("4,30,16", 41), ("16,12,8", 17), ("2,3,8", 39)])
+PHASE_SHIFTED = [("6,5,8", 21), ("10,9,16", 35), ("3,9,8", 17), ("12,3,8", 35), ("15,13,16", 35), ("9,17,8", 33),
+                 ("4,30,16", 41), ("16,12,8", 17), ("2,3,8", 39)]
+
+
+def _phase_shifted_rows(geom, win):
+    """the tile with whole window rows on the plain kernel, then phase-shifted with chunks of JC and the wave order off and on"""
+    XG, DG, JC = (int(v) for v in geom.split(","))
+    p = dict(winSize=win, maxDisparity=DG * 4 - 2, minDisparity=1, gammaC=7.0)
+    return [(form,) + SYNTH + (p,) for form in [F.workgroup_tile("%d,%d,0,8" % (XG, DG))] +
+            [F.pipe_tile(XG, DG, JC, dephase=dephase) for dephase in ("0", "1")]]
+
+
+@pytest.mark.parametrize("geom,win", PHASE_SHIFTED)
 def test_asw_phase_shifted_kernel_equals_the_plain_one(geom, win, ss, golden_inputs):
     """asw_aggregate_pipe_kernel (lanes along the disparity groups, plain LDS rows, waves 0-3 building before they
     aggregate, tail-merged tap-column chunks of 8 or 16) accumulates the same taps in the same order as
@@ -179,101 +186,117 @@ def test_asw_phase_shifted_kernel_equals_the_plain_one(geom, win, ss, golden_inp
     the wave order switched on and off, the maps are those of the plain kernel bit for bit (consistent mode: both
     argmins and the raw cost dump as well)"""
     a, b = golden_inputs("synth_96x128")
-    XG, DG, JC = (int(v) for v in geom.split(","))
-    maxd = DG * 4 - 2
-    m = ss.passive.StereoASW(winSize=win, maxDisparity=maxd, minDisparity=1, consistent=True, gammaC=7.0)
-    from simplestereo_amd import _native
-    H, W = a.shape[:2]
-
-    def costs():
-        c = np.empty((H, W, maxd), np.float32)
-        _native.check(_native.lib().ssamd_asw_costs(a.ctypes.data, b.ctypes.data, H, W, win, maxd, 1, 7.0, 17.5, c.ctypes.data, -1))
-        return c
-    _native.set_option("SSAMD_ASW_GEOM", "%d,%d,0,8" % (XG, DG))          # the tile, whole window rows, plain kernel
-    _native.set_option("SSAMD_ASW_PIPE", "0")
-    try:
-        want, want_c = m.compute(a, b), costs()
-        for dephase in ("0", "1"):
-            _native.set_option("SSAMD_ASW_PIPE", str(JC))
-            _native.set_option("SSAMD_ASW_DEPHASE", dephase)
-            got, got_c = m.compute(a, b), costs()
-            assert np.array_equal(got, want), (geom, win, dephase)
-            assert np.array_equal(got_c, want_c, equal_nan=True), (geom, win, dephase)
-    finally:
-        for k in ("SSAMD_ASW_GEOM", "SSAMD_ASW_PIPE", "SSAMD_ASW_DEPHASE"):
-            _native.set_option(k, None)
+    plain, *shifted = _phase_shifted_rows(geom, win)
+    p = plain[3]
+    m = ss.passive.StereoASW(consistent=True, **p)
+    with F.forced(*plain):
+        want, want_c = m.compute(a, b), F.cost_dump(a, b, p)
+    for row in shifted:
+        with F.forced(*row):
+            got, got_c = m.compute(a, b), F.cost_dump(a, b, p)
+        assert np.array_equal(got, want), (geom, win, row[0][0])
+        assert F.same_costs(got_c, want_c) == 0, (geom, win, row[0][0])
 
 
-@pytest.mark.parametrize("shape,win,maxd", [((48, 200), 35, 70), ((36, 1000), 27, 150), ((30, 2000), 35, 192)])
+TAD_VOLUME = [((48, 200), 35, 70), ((36, 1000), 27, 150), ((30, 2000), 35, 192)]
+
+
+def _tad_volume_rows(shape, win, maxd):
+    """the planner's phase-shifted kernel on the TAD volume, and building its e tiles itself"""
+    p = dict(winSize=win, maxDisparity=maxd)
+    return [((opts, dict(phase_shifted=1)), shape[1], shape[0], p) for opts in ({}, dict(SSAMD_ASW_EVOL="0"))]
+
+
+@pytest.mark.parametrize("shape,win,maxd", TAD_VOLUME)
 def test_asw_tad_volume_equals_the_in_kernel_e_tiles(shape, win, maxd, ss):
     """the phase-shifted kernel fed by LDS-DMA from the pre-computed TAD volume (asw_tad_volume_kernel: 16-byte stores,
     rows of whole 16-byte blocks) computes the map of the same kernel building its e tiles itself (SSAMD_ASW_EVOL=0)"""
     import torch
-    from simplestereo_amd import _native
     from simplestereo_amd.synth import make_pair
     H, W = shape
     L, R, _ = make_pair(H, W, maxd, 21)
     tL, tR = torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda()
-    assert _native.asw_kernel_form(W, H, win, maxd, 0)["phase_shifted"] == 1
+    volume, in_kernel = _tad_volume_rows(shape, win, maxd)
     m = ss.passive.StereoASW(winSize=win, maxDisparity=maxd, consistent=True)
-    want = m.compute(tL, tR)
-    try:
-        _native.set_option("SSAMD_ASW_EVOL", "0")
+    with F.forced(*volume):
+        want = m.compute(tL, tR)
+    with F.forced(*in_kernel):
         assert torch.equal(m.compute(tL, tR), want)
-    finally:
-        _native.set_option("SSAMD_ASW_EVOL", None)
 
 
-@pytest.mark.parametrize("win,maxd,mind,consistent", [(35, 16, 0, False), (35, 16, 0, True), (21, 7, 0, True), (9, 3, 0, False),
-                                                       (15, 1, 1, True), (1, 12, 0, True), (5, 47, 0, True), (17, 36, 5, True),
-                                                       (11, 23, 9, True), (63, 20, 2, False),
-                                                       (35, 55, 0, True), (21, 66, 3, False), (15, 48, 0, True)])     # round 3: 49..64 disparities
+WAVE = [(35, 16, 0, False), (35, 16, 0, True), (21, 7, 0, True), (9, 3, 0, False),
+        (15, 1, 1, True), (1, 12, 0, True), (5, 47, 0, True), (17, 36, 5, True),
+        (11, 23, 9, True), (63, 20, 2, False),
+        (35, 55, 0, True), (21, 66, 3, False), (15, 48, 0, True)]     # round 3: 49..64 disparities
+
+
+def _wave_rows(win, maxd, mind):
+    """the workgroup kernels, then both register tiles of the wave kernel: the strip's left and right centres as one list of build
+    rounds (round 3, merged) and in separate rounds (round-2 form).  A tile that does not fit LDS for the window / range is left out
+    by the test (the planner then reports another wave_kernel)."""
+    p = dict(winSize=win, maxDisparity=maxd, minDisparity=mind, gammaC=6.0)
+    return [(form,) + SYNTH + (p,) for form in [F.NO_WAVE] +
+            [F.wave(rx, SSAMD_ASW_WAVE_MERGE=merge) for rx, merge in (("8", None), ("4", None), ("8", "0"), ("4", "0"))]]
+
+
+def _fits(row):
+    """does the wave kernel's tile of this row fit LDS?  Any other mismatch of the form is the test's failure."""
+    try:
+        with F.forced(*row):
+            return True
+    except F.FormMismatch as e:
+        if e.key != "wave_kernel":
+            raise
+        return False
+
+
+@pytest.mark.parametrize("win,maxd,mind,consistent", WAVE)
 def test_asw_wave_kernel_equals_the_workgroup_kernels(win, maxd, mind, consistent, ss, golden_inputs):
     """asw_aggregate_wave_kernel (small disparity ranges: a wave builds the support weights of its own strip, no
     workgroup barriers) accumulates the same taps in the same order as the workgroup kernels: with both register tiles
     forced, for ranges of 1..48 disparities, windows 1..63, minDisparity 0 and above, image widths that end
     inside a strip and images narrower than one strip, the maps -- consistent mode: both argmins, and the raw cost
     dump -- are those of the workgroup kernel bit for bit.  The class default (maxDisparity 16) runs this kernel."""
-    from simplestereo_amd import _native
     a, b = golden_inputs("synth_96x128")
     pairs = [(a, b), (np.ascontiguousarray(a[:50, :77]), np.ascontiguousarray(b[:50, :77])),
              (np.ascontiguousarray(a[:40, :23]), np.ascontiguousarray(b[:40, :23]))]
-    nD = maxd - mind + 1
-    assert _native.asw_kernel_form(1920, 1080, win, maxd, mind)["wave_kernel"] in (4, 8)
-    assert _native.asw_kernel_form(1920, 1080, 35, 16, 0)["wave_kernel"] == 4          # class default range (round 3: merged build rounds)
-    assert _native.asw_kernel_form(1920, 1080, 35, 20, 0)["wave_kernel"] == 8
-    assert _native.asw_kernel_form(1920, 1080, 35, 64, 0)["wave_kernel"] == 0
-    m = ss.passive.StereoASW(winSize=win, maxDisparity=maxd, minDisparity=mind, consistent=consistent, gammaC=6.0)
+    full_hd = lambda win, maxd, mind=0: F.planned(1920, 1080, dict(winSize=win, maxDisparity=maxd, minDisparity=mind))["wave_kernel"]   # noqa: E731
+    assert full_hd(win, maxd, mind) in (4, 8)
+    assert full_hd(35, 16) == 4          # class default range (round 3: merged build rounds)
+    assert full_hd(35, 20) == 8 and full_hd(35, 64) == 0
+    workgroup, *tiles = _wave_rows(win, maxd, mind)
+    p = workgroup[3]
+    m = ss.passive.StereoASW(consistent=consistent, **p)
 
     def run(L, R):
-        H, W = L.shape[:2]
-        c = np.empty((H, W, nD), np.float32)
-        _native.check(_native.lib().ssamd_asw_costs(L.ctypes.data, R.ctypes.data, H, W, win, maxd, mind, 6.0, 17.5, c.ctypes.data, -1))
-        return m.compute(L, R), c
-    try:
-        _native.set_option("SSAMD_ASW_WAVE", "0")
+        return m.compute(L, R), F.cost_dump(L, R, p)
+    with F.forced(*workgroup):
         want = [run(L, R) for L, R in pairs]
-        _native.set_option("SSAMD_ASW_WAVE", "1")
-        ran = 0
-        # both register tiles; the strip's left and right centres as one list of build rounds (round 3, merged) and in
-        # separate rounds (round-2 form)
-        for rx, merge in (("8", None), ("4", None), ("8", "0"), ("4", "0")):
-            _native.set_option("SSAMD_ASW_WAVE_RX", rx)
-            _native.set_option("SSAMD_ASW_WAVE_MERGE", merge)
-            if _native.asw_kernel_form(128, 96, win, maxd, mind)["wave_kernel"] != int(rx):
-                continue                                      # this tile does not fit LDS for the window / range
-            ran += 1
+    ran = 0
+    for row in tiles:
+        if not _fits(row):
+            continue                                      # this tile does not fit LDS for the window / range
+        ran += 1
+        with F.forced(*row):
             for (L, R), (wd, wc) in zip(pairs, want):
                 gd, gc = run(L, R)
-                assert np.array_equal(gd, wd), (rx, merge, L.shape)
-                assert np.array_equal(gc, wc, equal_nan=True), (rx, merge, L.shape)
-        assert ran >= 2
-    finally:
-        for k in ("SSAMD_ASW_WAVE", "SSAMD_ASW_WAVE_RX", "SSAMD_ASW_WAVE_MERGE"):
-            _native.set_option(k, None)
+                assert np.array_equal(gd, wd), (row[0][0], L.shape)
+                assert F.same_costs(gc, wc) == 0, (row[0][0], L.shape)
+    assert ran >= 2
 
 
-@pytest.mark.parametrize("maxd,win", [(7, 35), (16, 35), (39, 21), (60, 35)])
+FULL_WIDTH = [(7, 35), (16, 35), (39, 21), (60, 35)]
+
+
+def _full_width_rows(maxd, win):
+    """the workgroup kernels; both tiles of the wave kernel with 1, 2 and 4 waves per workgroup; the last of them not unrolled"""
+    p = dict(winSize=win, maxDisparity=maxd)
+    return [(form, 1920, 44, p) for form in [F.NO_WAVE] +
+            [F.wave(rx, SSAMD_ASW_WAVE_WG=wg) for rx, wg in (("8", "1"), ("4", "1"), ("8", "4"), ("4", "2"))] +
+            [F.wave("4", SSAMD_ASW_WAVE_WG="2", SSAMD_ASW_WAVE_UNROLL="0")]]
+
+
+@pytest.mark.parametrize("maxd,win", FULL_WIDTH)
 def test_asw_wave_kernel_full_width_rows(maxd, win, ss):
     """1920-column rows (20 strips of 96 columns / 15 of 128 / 34 of 56 plus a ragged last one; waves per workgroup 1, 2
     and 4): both tiles of the wave kernel give the map of the workgroup kernels bit for bit"""
@@ -282,45 +305,35 @@ def test_asw_wave_kernel_full_width_rows(maxd, win, ss):
     L, R, _ = make_pair(44, 1920, maxd, 11)
     tL, tR = torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda()
     m = ss.passive.StereoASW(winSize=win, maxDisparity=maxd, consistent=True)
-    try:
-        _native.set_option("SSAMD_ASW_WAVE", "0")
+    workgroup, *tiles = _full_width_rows(maxd, win)
+    with F.forced(*workgroup):
         want = m.compute(tL, tR)
-        _native.set_option("SSAMD_ASW_WAVE", "1")
-        for rx, wg in (("8", "1"), ("4", "1"), ("8", "4"), ("4", "2")):
-            _native.set_option("SSAMD_ASW_WAVE_RX", rx); _native.set_option("SSAMD_ASW_WAVE_WG", wg)
-            assert torch.equal(m.compute(tL, tR), want), (rx, wg)
-        _native.set_option("SSAMD_ASW_WAVE_UNROLL", "0")
-        assert torch.equal(m.compute(tL, tR), want)
-    finally:
-        for k in ("SSAMD_ASW_WAVE", "SSAMD_ASW_WAVE_RX", "SSAMD_ASW_WAVE_WG", "SSAMD_ASW_WAVE_UNROLL"):
-            _native.set_option(k, None)
+    for row in tiles:
+        with F.forced(*row):
+            assert torch.equal(m.compute(tL, tR), want), row[0][0]
+
+
+STRIPS = dict(winSize=13, maxDisparity=16)
 
 
 def test_asw_wave_kernel_strips_and_alternate_rows(ss, golden_inputs):
     """the wave kernel under the other entry points: a row strip with its halo equals the rows of the whole frame, the
     alternate-rows mode and the separate argmins equal those computed with the workgroup kernels"""
-    from simplestereo_amd import _native
     import torch
     a, b = golden_inputs("synth_96x128")
     tL, tR = torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()
-    m = ss.passive.StereoASW(winSize=13, maxDisparity=16, consistent=True)
-    alt = ss.passive.StereoASW(winSize=13, maxDisparity=16, alternate=True)
-    try:
-        _native.set_option("SSAMD_ASW_WAVE", "0")
+    m = ss.passive.StereoASW(consistent=True, **STRIPS)
+    alt = ss.passive.StereoASW(alternate=True, **STRIPS)
+    with F.forced(F.NO_WAVE, *SYNTH, STRIPS):
         want, want_alt = m.compute(tL, tR), alt.compute(tL, tR)
         want_strip = m._compute_device(tL[20:70].contiguous(), tR[20:70].contiguous(), out_row0=6, out_rows=38)
-        _native.set_option("SSAMD_ASW_WAVE", "1")
-        for rx in ("8", "4"):
-            _native.set_option("SSAMD_ASW_WAVE_RX", rx)
-            assert _native.asw_kernel_form(128, 96, 13, 16, 0)["wave_kernel"] == int(rx)
+    for rx in ("8", "4"):
+        with F.forced(F.wave(rx), *SYNTH, STRIPS):
             assert torch.equal(m.compute(tL, tR), want)
             assert torch.equal(alt.compute(tL, tR), want_alt)
             got_strip = m._compute_device(tL[20:70].contiguous(), tR[20:70].contiguous(), out_row0=6, out_rows=38)
             assert torch.equal(got_strip, want_strip)
             assert torch.equal(got_strip, want[26:64])
-    finally:
-        for k in ("SSAMD_ASW_WAVE", "SSAMD_ASW_WAVE_RX"):
-            _native.set_option(k, None)
 
 
 @pytest.mark.parametrize("H,W,maxd,shift", [(1080, 1920, 192, 150), (2160, 4096, 256, 233)])
@@ -353,12 +366,20 @@ def test_asw_full_size_configs_3_and_5_known_shift_and_strip_invariance(H, W, ma
     assert torch.equal(strip, d[r0:r0 + rows])
 
 
+AUTOTUNE = [dict(winSize=21, maxDisparity=39), dict(winSize=35, maxDisparity=16, consistent=True),
+            dict(winSize=9, maxDisparity=70, minDisparity=3), dict(winSize=15, maxDisparity=24, alternate=True)]
+
+
+def _unrelated_rows():
+    """a forced geometry that has nothing to do with the tuner's, on the 120-column crop"""
+    return [(F.tile("3,5,8"), 120, 96, p) for p in AUTOTUNE]
+
+
 def test_autotune_changes_the_geometry_never_the_map(ss, golden_inputs):
     """with autotuning on, the first call of a shape times ~10 candidate geometries (8- and 4-column tiles, chunked
     and unchunked, key path and direct path) on the call's buffers; the map must be the one of the model's choice"""
     a, b = golden_inputs("synth_96x128")
-    cases = [dict(winSize=21, maxDisparity=39), dict(winSize=35, maxDisparity=16, consistent=True),
-             dict(winSize=9, maxDisparity=70, minDisparity=3), dict(winSize=15, maxDisparity=24, alternate=True)]
+    cases = AUTOTUNE
     want = [ss.passive.StereoASW(**p).compute(a, b) for p in cases]
     before = ss.passive.set_autotune(True)
     try:
@@ -372,11 +393,10 @@ def test_autotune_changes_the_geometry_never_the_map(ss, golden_inputs):
     from oracle import oracle
     for p, g1, g2 in zip(cases, got_first, got_again):
         assert np.array_equal(g1, g2)
-    _native.set_option("SSAMD_ASW_GEOM", "3,5,8")           # an unrelated forced geometry computes the same maps
-    try:
-        forced = [ss.passive.StereoASW(**p).compute(a2, b2) for p in cases]
-    finally:
-        _native.set_option("SSAMD_ASW_GEOM", None)
+    forced = []                                             # an unrelated forced geometry computes the same maps
+    for row in _unrelated_rows():
+        with F.forced(*row):
+            forced.append(ss.passive.StereoASW(**row[3]).compute(a2, b2))
     for g1, f in zip(got_first, forced):
         assert np.array_equal(g1, f)
     assert all(w.shape == (96, 128) for w in want)
@@ -411,30 +431,30 @@ def test_asw_when_the_tad_volume_allocation_really_fails(ss):
     L, R, _ = make_pair(40, 300, 70, 9)
     tL, tR = torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda()
     m = ss.passive.StereoASW(winSize=35, maxDisparity=70)
-    assert _native.asw_kernel_form(300, 40, 35, 70, 0)["phase_shifted"] == 1
+    assert F.planned(300, 40, dict(winSize=35, maxDisparity=70))["phase_shifted"] == 1
     want = m.compute(tL, tR)
-    n0 = _native.counter("evol_fallbacks")
     with _native.options(SSAMD_ASW_EVOL_FAIL="1"):
-        got = m.compute(tL, tR)
+        with F.counted("evol_fallbacks") as n:
+            got = m.compute(tL, tR)
         assert torch.equal(got, want)
-        assert _native.counter("evol_fallbacks") == n0 + 1
+        assert n.delta == 1
         # the small-range wave kernel cannot run without its volume: the call falls back to the workgroup geometry stored
         # next to the wave geometry (round 5; a clean error until round 4) -- same map, the fallback counted, no stale HIP
         # error afterwards; a first call of a shape under the tuner simply ends up on a workgroup candidate
         small = ss.passive.StereoASW(winSize=35, maxDisparity=16)
         prev = _native.lib().ssamd_autotune(0)
         try:
-            n1 = _native.counter("evol_fallbacks")
-            untuned = small.compute(tL, tR)
-            assert _native.counter("evol_fallbacks") > n1
+            with F.counted("evol_fallbacks") as n:
+                untuned = small.compute(tL, tR)
+            assert n.delta > 0
         finally:
             _native.lib().ssamd_autotune(prev)
         tuned = small.compute(tL, tR)
         assert torch.equal(untuned, tuned)
-    n2 = _native.counter("evol_fallbacks")
-    assert torch.equal(small.compute(tL, tR), tuned)          # same map from the wave kernel once the volume can be had again
-    assert torch.equal(m.compute(tL, tR), want)
-    assert _native.counter("evol_fallbacks") == n2 and _native.counter("evol_bytes") > 0
+    with F.counted("evol_fallbacks") as n:
+        assert torch.equal(small.compute(tL, tR), tuned)      # same map from the wave kernel once the volume can be had again
+        assert torch.equal(m.compute(tL, tR), want)
+    assert n.delta == 0 and _native.counter("evol_bytes") > 0
     assert ss.passive.StereoASW(winSize=35, maxDisparity=16).compute(tL, tR).shape == (40, 300)
 
 
@@ -450,26 +470,21 @@ def test_asw_half_width_tiles_for_the_last_partial_round(shape, maxd, consistent
     H, W = shape
     L, R, _ = make_pair(H, W, maxd, 21)
     tL, tR = torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda()
-    m = ss.passive.StereoASW(winSize=35, maxDisparity=maxd, consistent=consistent)
-
-    def costs():
-        c = np.empty((H, W, maxd + 1), np.float32)
-        _native.check(_native.lib().ssamd_asw_costs(L.ctypes.data, R.ctypes.data, H, W, 35, maxd, 0, 5.0, 17.5, c.ctypes.data, -1))
-        return c
-    with _native.options(SSAMD_ASW_TAIL="0", SSAMD_AUTOTUNE="0"):
-        n0 = _native.counter("tail_splits")
+    p = dict(winSize=35, maxDisparity=maxd)
+    m = ss.passive.StereoASW(consistent=consistent, **p)
+    with _native.options(SSAMD_ASW_TAIL="0", SSAMD_AUTOTUNE="0"), F.counted("tail_splits") as n:
         want = m.compute(tL, tR)
-        cw = costs() if not consistent else None
-        assert _native.counter("tail_splits") == n0
+        cw = F.cost_dump(L, R, p) if not consistent else None
+    assert n.delta == 0
     opts = dict(SSAMD_AUTOTUNE="0")
     if force:
         opts["SSAMD_ASW_TAIL"] = force
     with _native.options(**opts):
-        n0 = _native.counter("tail_splits")
-        got = m.compute(tL, tR)
-        assert _native.counter("tail_splits") == n0 + 1, "the split did not happen: the test does not test it"
+        with F.counted("tail_splits") as n:
+            got = m.compute(tL, tR)
+        assert n.delta == 1, "the split did not happen: the test does not test it"
         if cw is not None:
-            assert np.array_equal(costs(), cw, equal_nan=True)
+            assert F.same_costs(F.cost_dump(L, R, p), cw) == 0
     assert torch.equal(got, want)
 
 
@@ -496,8 +511,17 @@ def test_tad_volume_is_not_released_on_every_switch_of_shape(ss):
     assert _native.counter("evol_bytes") < cap
 
 
-@pytest.mark.parametrize("win,maxd,mind,consistent", [(35, 16, 0, False), (35, 16, 0, True), (15, 17, 0, True), (7, 21, 5, False), (63, 18, 2, True),
-                                                       (11, 22, 5, True)])
+SIX = [(35, 16, 0, False), (35, 16, 0, True), (15, 17, 0, True), (7, 21, 5, False), (63, 18, 2, True), (11, 22, 5, True)]
+
+
+def _six_rows(win, maxd, mind):
+    """the workgroup kernels, three groups of six per lane, five groups of four: asked at the 700 x 37 frame.  The test skips a
+    window whose 4-column tile does not fit LDS."""
+    p = dict(winSize=win, maxDisparity=maxd, minDisparity=mind, gammaC=6.0)
+    return [(form, 700, 37, p) for form in (F.NO_WAVE, "wave6", "wave4x5")]
+
+
+@pytest.mark.parametrize("win,maxd,mind,consistent", SIX)
 def test_asw_wave_kernel_six_disparities_per_lane(win, maxd, mind, consistent, ss, golden_inputs):
     """asw_aggregate_wave6_kernel (17 / 18 disparities -- the class default maxDisparity = 16 -- as three groups of SIX per
     lane: 8-byte e slots, nine right weights from an 8-byte-aligned address) computes the maps and the raw costs of the
@@ -509,31 +533,23 @@ def test_asw_wave_kernel_six_disparities_per_lane(win, maxd, mind, consistent, s
     L2, R2, _ = make_pair(37, 700, maxd, 5)
     pairs = [(a, b), (np.ascontiguousarray(a[:50, :77]), np.ascontiguousarray(b[:50, :77])), (L2, R2),
              (np.ascontiguousarray(a[:9, :23]), np.ascontiguousarray(b[:9, :23]))]
-    m = ss.passive.StereoASW(winSize=win, maxDisparity=maxd, minDisparity=mind, consistent=consistent, gammaC=6.0)
+    workgroup, six_row, four_row = _six_rows(win, maxd, mind)
+    p = workgroup[3]
+    m = ss.passive.StereoASW(consistent=consistent, **p)
 
     def run(L, R):
-        H, W = L.shape[:2]
-        c = np.empty((H, W, nD), np.float32)
-        _native.check(_native.lib().ssamd_asw_costs(L.ctypes.data, R.ctypes.data, H, W, win, maxd, mind, 6.0, 17.5, c.ctypes.data, -1))
-        return m.compute(L, R), c
-    try:
-        _native.set_option("SSAMD_ASW_WAVE", "0")
+        return m.compute(L, R), F.cost_dump(L, R, p)
+    with F.forced(*workgroup):
         want = [run(L, R) for L, R in pairs]
-        _native.set_option("SSAMD_ASW_WAVE", "1")
-        _native.set_option("SSAMD_ASW_WAVE_RX", "4")
-        if _native.asw_kernel_form(700, 37, win, maxd, mind)["wave_kernel"] != 4:
-            pytest.skip("the 4-column tile does not fit LDS for this window")
-        assert _native.asw_geometry(700, 37, win, maxd, mind)["chunk_d"] == 18          # three groups of six
+    if not _fits(six_row):
+        pytest.skip("the 4-column tile does not fit LDS for this window")
+    with F.forced(*six_row):                                # three groups of six
         six = [run(L, R) for L, R in pairs]
-        _native.set_option("SSAMD_ASW_WAVE_RD", "4")
-        assert _native.asw_geometry(700, 37, win, maxd, mind)["chunk_d"] == 20          # five groups of four
+    with F.forced(*four_row):                               # five groups of four
         four = [run(L, R) for L, R in pairs]
-        for (wd, wc), (sd, sc), (fd, fc) in zip(want, six, four):
-            assert np.array_equal(sd, wd) and np.array_equal(fd, wd)
-            assert np.array_equal(sc, wc, equal_nan=True) and np.array_equal(fc, wc, equal_nan=True)
-    finally:
-        for k in ("SSAMD_ASW_WAVE", "SSAMD_ASW_WAVE_RX", "SSAMD_ASW_WAVE_RD"):
-            _native.set_option(k, None)
+    for (wd, wc), (sd, sc), (fd, fc) in zip(want, six, four):
+        assert np.array_equal(sd, wd) and np.array_equal(fd, wd)
+        assert F.same_costs(sc, wc) == 0 and F.same_costs(fc, wc) == 0
 
 
 @pytest.mark.parametrize("shape,win,maxd,mind,consistent", [((48, 160), 65, 20, 0, False), ((60, 140), 99, 12, 2, True),
@@ -552,9 +568,7 @@ def test_asw_windows_beyond_63(shape, win, maxd, mind, consistent, ss):
     ref, cref = oracle.asw(L, R, consistent=False, return_costs=True, **p)
     if consistent:
         ref = oracle.asw(L, R, consistent=True, **p)
-    nD = maxd - mind + 1
-    c = np.empty((H, W, nD), np.float32)
-    _native.check(_native.lib().ssamd_asw_costs(L.ctypes.data, R.ctypes.data, H, W, win, maxd, mind, 7.0, 40.0, c.ctypes.data, -1))
+    c = F.cost_dump(L, R, p)
     assert np.array_equal(np.isnan(c), np.isnan(cref))
     ok = ~np.isnan(cref)
     assert (np.abs(c[ok] - cref[ok]) / np.maximum(1.0, np.abs(cref[ok]))).max() <= 1e-4
@@ -564,3 +578,18 @@ def test_asw_windows_beyond_63(shape, win, maxd, mind, consistent, ss):
     if win <= 127:          # (the closed-form oracle needs seconds for these; the literal relaxation would need hours)
         g = dict(winSize=win, maxDisparity=maxd, minDisparity=mind, gamma=10, fMax=120, iterations=3)
         assert np.array_equal(ss.passive.StereoGSW(**g).compute(L, R), oracle.gsw(L, R, closed=True, **g))
+
+
+def forced_rows():
+    """every forced form of this file, as (form, W, H, params): tests/test_asw_forms_cpu.py asks the planner for each"""
+    rows = [row for geom in GEOMS for row in _geometry_rows(geom)]
+    rows += [row for r in PHASE_SHIFTED for row in _phase_shifted_rows(*r)] + [row for r in TAD_VOLUME for row in _tad_volume_rows(*r)]
+    rows += [_wave_rows(*r[:3])[0] for r in WAVE] + [row for r in FULL_WIDTH for row in _full_width_rows(*r)]
+    rows += [(form,) + SYNTH + (STRIPS,) for form in (F.NO_WAVE, F.wave("8"), F.wave("4"))]
+    return rows + _unrelated_rows() + [_six_rows(*r[:3])[0] for r in SIX]
+
+
+def rows_that_may_not_fit():
+    """wave-kernel tiles that the tests leave out, or skip for, where they do not fit LDS; the tests that need them are listed
+    with the least number of rows that must fit"""
+    return [(_wave_rows(*r[:3])[1:], 2) for r in WAVE] + [(_six_rows(*r[:3])[1:], 0) for r in SIX]

@@ -3,7 +3,9 @@ passive.py:43-46, without code -- so there is no reference output and this mode 
 own CPU restatement built from the reference-exact pieces, oracle.asw_alternate, and by its properties)."""
 import numpy as np
 import pytest
-from simplestereo_amd import _native      # noqa: E402  (tuning options: _native.set_option)
+from simplestereo_amd import _native
+
+import _asw_forms as F
 
 pytestmark = pytest.mark.gpu
 
@@ -112,11 +114,8 @@ def test_alternate_full_queue_falls_back_to_in_place_evaluation(ss, golden_input
     m = ss.passive.StereoASW(winSize=15, maxDisparity=16, alternate=True)
     want = m.compute(a, b)
     for cap in ("1", "37", "300"):
-        _native.set_option("SSAMD_ALT_QUEUE_CAP", cap)
-        try:
+        with _native.options(SSAMD_ALT_QUEUE_CAP=cap):
             got = m.compute(a, b)
-        finally:
-            _native.set_option("SSAMD_ALT_QUEUE_CAP", None)
         assert np.array_equal(got, want), cap
 
 
@@ -159,18 +158,23 @@ def test_alternate_fuzz_vs_restatement(case, ss):
     assert bad == 0, (case, bad)
 
 
+# Dc = 20: two chunks for 40 disparities, chunked tap staging
+SEVERAL_CHUNKS = (F.also(F.tile("6,5,8"), n_chunks=2), 128, 96, dict(winSize=21, maxDisparity=39))
+
+
+def forced_rows():
+    return [SEVERAL_CHUNKS]
+
+
 def test_alternate_with_several_disparity_chunks_goes_through_the_key_path(ss, golden_inputs):
     """a forced small tile splits the disparity range over several workgroups: the even rows are then merged
     through the WTA keys and decoded, instead of being written by the aggregation kernel -- same map"""
     import os
     a, b = golden_inputs("synth_96x128")
-    m = ss.passive.StereoASW(winSize=21, maxDisparity=39, alternate=True)
+    m = ss.passive.StereoASW(alternate=True, **SEVERAL_CHUNKS[3])
     want = m.compute(a, b)
-    _native.set_option("SSAMD_ASW_GEOM", "6,5,8")          # Dc = 20: two chunks for 40 disparities, chunked tap staging
-    try:
+    with F.forced(*SEVERAL_CHUNKS):
         got = m.compute(a, b)
-    finally:
-        _native.set_option("SSAMD_ASW_GEOM", None)
     assert np.array_equal(got, want)
 
 

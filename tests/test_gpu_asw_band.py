@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 
 import _asw_band_ref as B
+import _asw_forms as F
 import _tie_inputs as T
 
 pytestmark = pytest.mark.gpu
@@ -38,22 +39,6 @@ def ss():
     assert torch.cuda.is_available(), "-m gpu tests need a GPU"
     import simplestereo_amd
     return simplestereo_amd
-
-
-def _dump(L, R, p, opts, want=None):
-    """the cost dump of ssamd_asw_costs under `opts` (float32 array: costs, or the images' bit patterns under the hook)"""
-    from simplestereo_amd import _native
-    H, W = L.shape[:2]
-    c = np.empty((H, W, p["maxDisparity"] - p["minDisparity"] + 1), np.float32)
-    with _native.options(**opts):
-        if want is not None:
-            f = dict(_native.asw_kernel_form(W, H, p["winSize"], p["maxDisparity"], p["minDisparity"]))
-            f.update(_native.asw_geometry(W, H, p["winSize"], p["maxDisparity"], p["minDisparity"]))
-            for k, v in want.items():
-                assert (v(f[k]) if callable(v) else f[k] == v), ("the form did not run", k, f[k], p)
-        _native.check(_native.lib().ssamd_asw_costs(L.ctypes.data, R.ctypes.data, H, W, p["winSize"], p["maxDisparity"],
-                                                    p["minDisparity"], float(p["gammaC"]), float(p["gammaP"]), c.ctypes.data, -1))
-    return c
 
 
 @pytest.mark.parametrize("name", sorted(B.CASES))
@@ -84,15 +69,15 @@ def test_cost_images_against_the_band(name, ss):
     bar, bar_above = 2 * max(fx["emu_E_max"], B.E_FLOOR), 2 * max(fx["emu_E_max_above_zkey"], B.E_FLOOR)
     i64 = B.image64(cost)
     ds = B.first_minimum(cost)[..., None]
+    H, W = L.shape[:2]
     first = None
     for form in case["forms"]:
-        opts, want = B.FORMS[form]
-        i32 = B.image32(_dump(L, R, p, dict(opts, SSAMD_ASW_COST_KEYS="1"), want))
+        with F.forced(form, W, H, p):
+            i32, c = B.image32(F.cost_dump(L, R, p, keys=True)), F.cost_dump(L, R, p) if first is None else None
         assert np.array_equal(i32 < 0, np.isnan(cost)), (name, form, "candidates that exist")
         if first is None:
             first = (form, i32)
             # the hook changes what is written, nothing else: the float dump is the image's cost
-            c = _dump(L, R, p, opts)
             ok = i32 >= 0
             with np.errstate(invalid="ignore"):
                 low = np.where(ok, i32, 0).astype(np.uint32).view(np.float32)

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import _asw_band_ref as B
+import _asw_forms as F
 import _tie_inputs as T
 
 H, W, MAXD, SEED = 6, 96, 19, 3
@@ -19,7 +20,6 @@ WINDOWS = tuple(range(3, 18, 2))
 # SSAMD_ASW_GEOM = "XG,DG,JC,RX": 40- and 28-column tiles (the last one of a row partial), 12 disparities per chunk (two chunks,
 # the second reaching past maxDisparity); JC 0 = whole window rows
 GEOMS = {8: ("5,3,0,8", "5,3,8,8"), 4: ("7,3,0,4", "7,3,4,4")}
-WORKGROUP = dict(SSAMD_ASW_WAVE="0", SSAMD_ASW_PIPE="0")
 OC = T.OracleCache()
 
 
@@ -27,21 +27,28 @@ def _params(win):
     return dict(winSize=win, maxDisparity=MAXD, minDisparity=0, gammaC=5.0, gammaP=17.5)
 
 
-def _forms(win, opts):
-    from simplestereo_amd import _native
-    with _native.options(**opts):
-        f = dict(_native.asw_kernel_form(W, H, win, MAXD, 0))
-        f.update(_native.asw_geometry(W, H, win, MAXD, 0))
-    return f
+def _tile(win, geom):
+    """the workgroup form on a forced tile, several tiles to a row"""
+    return F.also(F.workgroup_tile(geom, win=win), grid_x=lambda n: n > 1)
+
+
+def _plan(win, geom):
+    with F.forced(_tile(win, geom), W, H, _params(win)) as f:
+        return f
+
+
+def forced_rows():
+    """every form the sweep forces, as (form, W, H, params): tests/test_asw_forms_cpu.py asks the planner for each"""
+    for win in WINDOWS:
+        for form in [F.wave(4), F.wave(8)] + [_tile(win, geom) for geoms in GEOMS.values() for geom in geoms]:
+            yield form, W, H, _params(win)
 
 
 def segment_lengths(win, geom, rx):
     """the tap-column segments one weight-build task covers, per chunk of a window row: asw_layout_e's balance rule
     (the cheapest of 1 .. 8 segments per chunk, a round of tasks costing the segment length rounded up to ASW_WB, plus 2)"""
-    f = _forms(win, dict(WORKGROUP, SSAMD_ASW_GEOM=geom))
-    assert f["phase_shifted"] == 0 and f["wave_kernel"] == 0 and f["tile_columns"] == rx, f
-    jc_opt = int(geom.split(",")[2])
-    assert f["chunk_columns"] == (jc_opt if 0 < jc_opt < win else 0), f
+    f = _plan(win, geom)
+    assert f["tile_columns"] == rx, f
     wcols = f["chunk_columns"] or win
     ncen = 2 * f["tile_x"] + f["chunk_d"] - 1               # left centres Tx, right centres Tx + Dc - 1
     best = None
@@ -69,16 +76,7 @@ def test_the_sweep_covers_every_remainder_of_a_segment_on_both_register_tiles():
         assert {r for r, _ in seen} == {0, 1, 2, 3}, (rx, sorted(seen))
         # a remainder after whole batches and a segment that is nothing but a remainder
         assert {r for r, whole in seen if whole and r} and {r for r, whole in seen if not whole}, (rx, sorted(seen))
-        assert any(int(g.split(",")[2]) and _forms(win, dict(WORKGROUP, SSAMD_ASW_GEOM=g))["chunk_columns"] for g in geoms for win in WINDOWS)
-
-
-def _images(L, R, p, opts):
-    from simplestereo_amd import _native
-    c = np.empty((H, W, MAXD + 1), np.float32)
-    with _native.options(SSAMD_ASW_COST_KEYS="1", **opts):
-        _native.check(_native.lib().ssamd_asw_costs(L.ctypes.data, R.ctypes.data, H, W, p["winSize"], MAXD, 0, float(p["gammaC"]),
-                                                    float(p["gammaP"]), c.ctypes.data, -1))
-    return B.image32(c)
+        assert any(int(g.split(",")[2]) and _plan(win, g)["chunk_columns"] for g in geoms for win in WINDOWS)
 
 
 @pytest.mark.gpu
@@ -93,20 +91,17 @@ def test_workgroup_build_against_the_wave_kernel_and_the_oracle(win):
     ref = OC.asw(L, R, **p)
     wave = {}
     for rx in (4, 8):
-        opts = dict(SSAMD_ASW_WAVE="1", SSAMD_ASW_WAVE_RX=str(rx))
-        assert _forms(win, opts)["wave_kernel"] == rx
-        wave[rx] = _images(L, R, p, opts)
+        with F.forced(F.wave(rx), W, H, p):
+            wave[rx] = B.image32(F.cost_dump(L, R, p, keys=True))
     assert np.array_equal(wave[4], wave[8])
     assert np.any(wave[4] >= 0) and np.any(wave[4] < 0)              # candidates that exist, and the left border's that do not
     for rx, geoms in GEOMS.items():
         for geom in geoms:
-            opts = dict(WORKGROUP, SSAMD_ASW_GEOM=geom)
-            f = _forms(win, opts)
-            assert f["phase_shifted"] == 0 and f["wave_kernel"] == 0 and f["tile_columns"] == rx and f["grid_x"] > 1, f
-            img = _images(L, R, p, opts)
-            for wrx in (4, 8):
-                assert np.array_equal(img, wave[wrx]), (win, geom, "wave", wrx, int(np.count_nonzero(img != wave[wrx])))
-            with _native.options(**opts):
+            with F.forced(_tile(win, geom), W, H, p) as f:
+                assert f["tile_columns"] == rx, f
+                img = B.image32(F.cost_dump(L, R, p, keys=True))
                 d = ss.passive.StereoASW(**p).compute(L, R)
                 assert _native.counter("exact_overflow") == 0
+            for wrx in (4, 8):
+                assert np.array_equal(img, wave[wrx]), (win, geom, "wave", wrx, int(np.count_nonzero(img != wave[wrx])))
             assert np.array_equal(d, ref), (win, geom, int(np.count_nonzero(d != ref)))

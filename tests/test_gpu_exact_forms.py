@@ -13,6 +13,7 @@ import os
 import numpy as np
 import pytest
 
+import _asw_forms as F
 import _tie_inputs as T
 
 pytestmark = pytest.mark.gpu
@@ -33,13 +34,12 @@ def _n(native):
     return {k: native.counter(k) for k in ("exact_overflow", "exact_entries", "exact_flagged_left", "exact_flagged_right")}
 
 
-def _case(ss, tag, L, R, p, opts, check=None):
-    """one (input, params) under `opts`: the default map is the oracle's; returns (n32, flagged right)"""
+def _case(ss, tag, L, R, p, form):
+    """one (input, params) under `form` (of _asw_forms; bare options force no kernel form): the default map is the oracle's;
+    returns (n32, flagged right)"""
     from simplestereo_amd import _native
     H, W = L.shape[:2]
-    with _native.options(**opts):
-        if check is not None:
-            check(W, H, p)
+    with (_native.options(**form) if isinstance(form, dict) else F.forced(form, W, H, p)):
         d = ss.passive.StereoASW(**p).compute(L, R)
         c = _n(_native)
         d32 = ss.passive.StereoASW(exact=False, **p).compute(L, R)
@@ -53,13 +53,13 @@ def _case(ss, tag, L, R, p, opts, check=None):
     return n32, c["exact_flagged_right"]
 
 
-def _matrix(ss, tag, opts, check, inputs):
+def _matrix(ss, tag, form, inputs):
     """every input, plain and consistent; the teeth of the form"""
     n32, fr = 0, 0
     for kind, H, W, p in inputs:
         L, R = T.pair(kind, H, W, p["maxDisparity"], seed=3)
         for cons in (False, True):
-            a, b = _case(ss, tag, L, R, dict(p, consistent=cons, minDisparity=p.get("minDisparity", 0), gammaP=17.5), opts, check)
+            a, b = _case(ss, tag, L, R, dict(p, consistent=cons, minDisparity=p.get("minDisparity", 0), gammaP=17.5), form)
             n32 += a
             fr = max(fr, b) if cons else fr
     assert n32 > 0, ("no case of this form has a pixel where the fp32 map differs from the oracle: the case has no teeth", tag)
@@ -72,29 +72,19 @@ def _inputs(win, maxd, H=24, W=128):
             ("patches", H, W, dict(winSize=win, maxDisparity=maxd, gammaC=0.7))]
 
 
-def _form(**want):
-    """check: asw_kernel_form / asw_geometry of the call's shape under the options hold `want`"""
-    def check(W, H, p):
-        from simplestereo_amd import _native
-        f = dict(_native.asw_kernel_form(W, H, p["winSize"], p["maxDisparity"], p["minDisparity"]))
-        f.update(_native.asw_geometry(W, H, p["winSize"], p["maxDisparity"], p["minDisparity"]))
-        for k, v in want.items():
-            assert (v(f[k]) if callable(v) else f[k] == v), ("the form did not run", k, f[k], v, p)
-    return check
-
-
 # ---- workgroup kernel (asw_aggregate_kernel): 8- / 4-column tiles, whole window rows and chunks of 4 / 8 / 16, one e tile, XOR rows
-WG = dict(SSAMD_ASW_WAVE="0", SSAMD_ASW_PIPE="0")
 WORKGROUP = [("6,5,0,8", 8, 0, {}), ("6,5,8,8", 8, 8, {}), ("10,9,16,8", 8, 16, {}), ("12,5,0,4", 4, 0, {}), ("7,9,8,4", 4, 8, {}),
              ("20,3,4,4", 4, 4, {}), ("6,5,8,8", 8, 8, dict(SSAMD_ASW_NO_E2="1")),
              ("6,5,8,8", 8, 8, dict(SSAMD_ASW_NO_E2="1", SSAMD_ASW_XOR_ONLY="1"))]
 
 
+def _workgroup(geom, rx, jc, extra):
+    return F.also(F.workgroup_tile(geom, **extra), tile_columns=rx, chunk_columns=jc), _inputs(21, int(geom.split(",")[1]) * 4 - 1)
+
+
 @pytest.mark.parametrize("geom,rx,jc,extra", WORKGROUP)
 def test_workgroup_kernel(geom, rx, jc, extra, ss):
-    DG = int(geom.split(",")[1])
-    _matrix(ss, "workgroup %s %s" % (geom, extra), dict(WG, SSAMD_ASW_GEOM=geom, **extra),
-            _form(phase_shifted=0, wave_kernel=0, tile_columns=rx, chunk_columns=jc), _inputs(21, DG * 4 - 1))
+    _matrix(ss, "workgroup %s %s" % (geom, extra), *_workgroup(geom, rx, jc, extra))
 
 
 # ---- phase-shifted kernel (asw_aggregate_pipe_kernel): chunks of 8 / 16, wave order, TAD volume or in-kernel e tiles
@@ -103,36 +93,38 @@ PIPE = [("6,5,0,8", 21, "8", "0", {}), ("6,5,0,8", 21, "8", "1", {}), ("10,9,0,8
         ("6,5,0,8", 21, "8", "1", dict(SSAMD_ASW_EVOL_MAX_MB="1"))]
 
 
+def _pipe(geom, win, jc, dephase, extra):
+    XG, DG = (int(v) for v in geom.split(",")[:2])
+    return F.pipe_tile(XG, DG, int(jc), dephase=dephase, **extra), _inputs(win, DG * 4 - 2, H=16)
+
+
 @pytest.mark.parametrize("geom,win,jc,dephase,extra", PIPE)
 def test_phase_shifted_kernel(geom, win, jc, dephase, extra, ss):
-    DG = int(geom.split(",")[1])
-    opts = dict(SSAMD_ASW_WAVE="0", SSAMD_ASW_GEOM=geom, SSAMD_ASW_PIPE=jc, SSAMD_ASW_DEPHASE=dephase, **extra)
-    _matrix(ss, "phase-shifted %s JC %s dephase %s %s" % (geom, jc, dephase, extra), opts,
-            _form(phase_shifted=1, chunk_columns=int(jc), build_first_waves=int(dephase)), _inputs(win, DG * 4 - 2, H=16))
+    _matrix(ss, "phase-shifted %s JC %s dephase %s %s" % (geom, jc, dephase, extra), *_pipe(geom, win, jc, dephase, extra))
+
+
+TAIL = F.pipe_tile(4, 5, 8, SSAMD_ASW_TAIL="1", SSAMD_AUTOTUNE="0")
+TAIL_PARAMS = dict(winSize=13, maxDisparity=19, minDisparity=0, gammaC=0.7, gammaP=17.5)
+TAIL_ROWS = range(32, 689, 8)
 
 
 def test_half_width_tail_tiles(ss):
     """SSAMD_ASW_TAIL=1: the smallest row count (8-row steps) whose launch has a last round at most half full on this device"""
-    from simplestereo_amd import _native
-    opts = dict(SSAMD_ASW_WAVE="0", SSAMD_ASW_GEOM="4,5,0,8", SSAMD_ASW_PIPE="8", SSAMD_ASW_TAIL="1", SSAMD_AUTOTUNE="0")
-    p = dict(winSize=13, maxDisparity=19, minDisparity=0, gammaC=0.7, gammaP=17.5)
-    W, found = 128, None
-    with _native.options(**opts):
-        for H in range(32, 689, 8):
-            L, R = T.pair("quantised", H, W, p["maxDisparity"], seed=3)
-            n0 = _native.counter("tail_splits")
+    p, W, found = TAIL_PARAMS, 128, None
+    for H in TAIL_ROWS:
+        L, R = T.pair("quantised", H, W, p["maxDisparity"], seed=3)
+        with F.forced(TAIL, W, H, p), F.counted("tail_splits") as n:
             ss.passive.StereoASW(**p).compute(L, R)
-            if _native.counter("tail_splits") == n0 + 1:
-                found = H
-                break
+        if n.delta == 1:
+            found = H
+            break
     assert found is not None, "no launch of up to 688 rows split its last round: the tail tiles were not tested"
     L, R = T.pair("quantised", found, W, p["maxDisparity"], seed=3)
     n32 = 0
     for cons in (False, True):
-        with _native.options(**opts):
-            n0 = _native.counter("tail_splits")
+        with F.forced(TAIL, W, found, p), F.counted("tail_splits") as n:
             a, _ = _case(ss, "tail tiles (%d rows)" % found, L, R, dict(p, consistent=cons), {})
-            assert _native.counter("tail_splits") >= n0 + 1
+            assert n.delta >= 1
         n32 += a
     assert n32 > 0
 
@@ -143,43 +135,49 @@ WAVE = [("8", {}, 128, None), ("4", {}, 128, None), ("8", dict(SSAMD_ASW_WAVE_ME
         ("4", dict(SSAMD_ASW_WAVE_WG="4"), 1000, 256), ("8", dict(SSAMD_ASW_WAVE_UNROLL="0"), 128, None)]
 
 
+def _wave(rx, extra, W, threads):
+    form = F.wave(rx, **extra)
+    return F.also(form, threads=threads) if threads else form, _inputs(9, 15, H=8 if W >= 1000 else 24, W=W)
+
+
 @pytest.mark.parametrize("rx,extra,W,threads", WAVE)
 def test_wave_kernel(rx, extra, W, threads, ss):
-    want = dict(wave_kernel=int(rx))
-    if threads:
-        want["threads"] = threads
-    H = 8 if W >= 1000 else 24
-    _matrix(ss, "wave RX %s %s" % (rx, extra), dict(SSAMD_ASW_WAVE="1", SSAMD_ASW_WAVE_RX=rx, **extra), _form(**want),
-            _inputs(9, 15, H=H, W=W))
+    _matrix(ss, "wave RX %s %s" % (rx, extra), *_wave(rx, extra, W, threads))
 
 
-@pytest.mark.parametrize("maxd,rd,chunk", [(16, None, 18), (17, None, 18), (17, "4", 20)])
+WAVE6 = [(16, None, 18), (17, None, 18), (17, "4", 20)]
+
+
+def _wave6(maxd, rd, chunk):
+    return F.also(F.wave(4, SSAMD_ASW_WAVE_RD=rd), chunk_d=chunk), _inputs(9, maxd)
+
+
+@pytest.mark.parametrize("maxd,rd,chunk", WAVE6)
 def test_wave6_kernel(maxd, rd, chunk, ss):
     """17 / 18 disparities: three groups of six per lane (asw_aggregate_wave6_kernel); WAVE_RD=4: five groups of four"""
-    opts = dict(SSAMD_ASW_WAVE="1", SSAMD_ASW_WAVE_RX="4")
-    if rd:
-        opts["SSAMD_ASW_WAVE_RD"] = rd
-    _matrix(ss, "wave6 D%d RD %s" % (maxd, rd), opts, _form(wave_kernel=4, chunk_d=chunk), _inputs(9, maxd))
+    _matrix(ss, "wave6 D%d RD %s" % (maxd, rd), *_wave6(maxd, rd, chunk))
+
+
+CHUNKS = (({}, dict(n_chunks=lambda n: n > 1)), [("quantised", 8, 600, dict(winSize=5, maxDisparity=530, gammaC=0.7)),
+                                                ("black_margins", 8, 600, dict(winSize=5, maxDisparity=530, gammaC=5.0))])
 
 
 def test_disparity_range_over_several_chunks(ss):
     """531 disparities: several chunks merged by atomics (a merging call also without a right pass)"""
-    _matrix(ss, "531 disparities", {}, _form(n_chunks=lambda n: n > 1),
-            [("quantised", 8, 600, dict(winSize=5, maxDisparity=530, gammaC=0.7)),
-             ("black_margins", 8, 600, dict(winSize=5, maxDisparity=530, gammaC=5.0))])
+    _matrix(ss, "531 disparities", *CHUNKS)
 
 
 def test_window_of_65_on_black_margins(ss):
     """windows of 64 and more bypass asw_exact_zero_kernel's LDS tiles (EXACT_ZWIN_MAX): zero-cost pixels are escalated"""
-    _matrix(ss, "window 65", {}, None, [("black_margins", 20, 120, dict(winSize=65, maxDisparity=8, gammaC=5.0)),
-                                       ("quantised", 20, 120, dict(winSize=65, maxDisparity=8, gammaC=0.7))])
+    _matrix(ss, "window 65", {}, [("black_margins", 20, 120, dict(winSize=65, maxDisparity=8, gammaC=5.0)),
+                                 ("quantised", 20, 120, dict(winSize=65, maxDisparity=8, gammaC=0.7))])
 
 
 # ---- entry points and record producers at their default forms -----------------------------------------------------------------
 def test_prepass_unfused(ss):
     """SSAMD_ASW_PREPASS_FUSE=0: the records come from asw_prepass_kernel instead of bgr2lab_records_pair_kernel"""
-    _matrix(ss, "prepass unfused", dict(SSAMD_ASW_PREPASS_FUSE="0"), None, _inputs(15, 40, H=16, W=200))
-    _matrix(ss, "prepass fused (default)", {}, None, _inputs(15, 40, H=16, W=200))
+    _matrix(ss, "prepass unfused", dict(SSAMD_ASW_PREPASS_FUSE="0"), _inputs(15, 40, H=16, W=200))
+    _matrix(ss, "prepass fused (default)", {}, _inputs(15, 40, H=16, W=200))
 
 
 @pytest.mark.parametrize("cons", [False, True])
@@ -268,9 +266,7 @@ def test_devices_listed_twice(ss):
 
 
 # ---- a lone zero-cost winner (rule (d) of exact_near) --------------------------------------------------------------------------
-LONE_FORMS = [("wave", dict(SSAMD_ASW_WAVE="1", SSAMD_ASW_WAVE_RX="8"), dict(wave_kernel=8)),
-              ("workgroup", dict(SSAMD_ASW_WAVE="0", SSAMD_ASW_PIPE="0", SSAMD_ASW_GEOM="4,5,0,8"), dict(phase_shifted=0, wave_kernel=0)),
-              ("phase-shifted", dict(SSAMD_ASW_WAVE="0", SSAMD_ASW_PIPE="8", SSAMD_ASW_GEOM="4,5,0,8"), dict(phase_shifted=1))]
+LONE_FORMS = [("wave",) + F.wave(8), ("workgroup",) + F.workgroup_tile("4,5,0,8"), ("phase-shifted",) + F.pipe_tile(4, 5, 8)]
 
 
 @pytest.mark.parametrize("name,opts,want", LONE_FORMS)
@@ -283,11 +279,7 @@ def test_lone_zero_cost_winner(name, opts, want, ss):
     L, R, p = T.lone_zero_pair()
     H, W = L.shape[:2]
     x, d0, d1 = T.LZ_X, T.LZ_D0, T.LZ_D1
-    nD = p["maxDisparity"] + 1
-    c = np.empty((H, W, nD), np.float32)
-    _native.check(_native.lib().ssamd_asw_costs(L.ctypes.data, R.ctypes.data, H, W, p["winSize"], p["maxDisparity"], 0,
-                                                p["gammaC"], p["gammaP"], c.ctypes.data, -1))
-    row = c[0, x]
+    row = F.cost_dump(L, R, p)[0, x]
     _, c64 = oracle.asw(L, R, return_costs=True, **p)
     tol = T.tol(p["winSize"], p["gammaC"])
     print("lone zero: fp32 costs at X: D0 %r, D1 %r (image %d ulps above 0, tol %d); fp64: D0 %r, D1 %r" %
@@ -298,8 +290,7 @@ def test_lone_zero_cost_winner(name, opts, want, ss):
     for cons in (False, True):
         q = dict(p, consistent=cons)
         ref = oracle.asw(L, R, **q)
-        with _native.options(**opts):
-            _form(**want)(W, H, q)
+        with F.forced(opts, W, H, q, want):
             d = ss.passive.StereoASW(**q).compute(L, R)
             assert _native.counter("exact_overflow") == 0
             d32 = ss.passive.StereoASW(exact=False, **q).compute(L, R)
@@ -307,3 +298,14 @@ def test_lone_zero_cost_winner(name, opts, want, ss):
             assert int(d32[0, x]) == d0                                                 # the fp32 argmin alone is wrong here
             assert int(d[0, x]) == int(ref[0, x]) == d1, (name, int(d[0, x]))
         assert np.array_equal(d, ref), (name, cons, np.argwhere(d != ref).tolist())
+
+
+def forced_rows():
+    """every forced form of this file, as (form, W, H, params): tests/test_asw_forms_cpu.py asks the planner for each"""
+    rows = []
+    for form, inputs in ([_workgroup(*r) for r in WORKGROUP] + [_pipe(*r) for r in PIPE] + [_wave(*r) for r in WAVE] +
+                         [_wave6(*r) for r in WAVE6] + [CHUNKS]):
+        rows += [(form, W, H, p) for _, H, W, p in inputs]
+    rows += [(TAIL, 128, H, TAIL_PARAMS) for H in TAIL_ROWS]
+    L, _, p = T.lone_zero_pair()
+    return rows + [((opts, want), L.shape[1], L.shape[0], p) for _, opts, want in LONE_FORMS]

@@ -13,24 +13,37 @@ import numpy as np
 import pytest
 from simplestereo_amd import _native
 
+import _asw_forms as F
+
 pytestmark = pytest.mark.gpu
 
-HOOKS = ("SSAMD_ASW_GEOM", "SSAMD_ASW_PIPE", "SSAMD_ASW_STATIC", "SSAMD_ASW_WAVE")
-
-# name -> XG, DG, JC (tile of 8 XG columns x 4 DG disparities, tap-column chunks), H, W, win, minD, maxD, consistent
+# name -> tile (_asw_forms.PIPE_TILES: 8 XG columns x 4 DG disparities, tap-column chunks), H, W, win, minD, maxD, consistent
 CASES = {
-    "120x196": (15, 49, 16, 40, 250, 35, 0, 192, False),          # chunks 16 + 19
-    "120x196-win33": (15, 49, 16, 40, 250, 33, 0, 192, False),    # chunks 16 + 17: remainder 1
-    "120x196-minD3": (15, 49, 16, 40, 250, 35, 3, 195, False),
-    "216x68": (27, 17, 16, 24, 450, 35, 0, 64, False),            # 9 centre-waves on 8 waves
-    "88x260": (11, 65, 16, 24, 180, 35, 0, 256, False),
-    "generic-8-8-8-11": (6, 9, 8, 24, 100, 35, 0, 35, True),      # 3 centre-waves on one wave, chunks 8, 8, 8, 11
+    "120x196": ("120x196", 40, 250, 35, 0, 192, False),           # chunks 16 + 19
+    "120x196-win33": ("120x196", 40, 250, 33, 0, 192, False),     # chunks 16 + 17: remainder 1
+    "120x196-minD3": ("120x196", 40, 250, 35, 3, 195, False),
+    "216x68": ("216x68", 24, 450, 35, 0, 64, False),              # 9 centre-waves on 8 waves
+    "88x260": ("88x260", 24, 180, 35, 0, 256, False),
+    "generic-8-8-8-11": ("48x36", 24, 100, 35, 0, 35, True),      # 3 centre-waves on one wave, chunks 8, 8, 8, 11
 }
 # static = 1: the library's default, which picks the instantiation with compile-time strides whenever the planned strides equal
 # one of its tiles' (120 / 316 / 208, 88 / 348 / 272, 216 / 284 / 80: the first five cases; the test asserts the tile, the host
 # then has no other choice); static = 0 forces the generic instantiation on the same tile.  No static tile has the strides of
 # the last case, so it runs the generic instantiation either way and is listed once.
 PARAMS = [(name, static) for name in CASES for static in (1, 0) if not (name.startswith("generic") and static == 0)]
+
+
+def _forms(name, static):
+    """the two sides of a case as (form, W, H, params): the phase-shifted kernel, and the round-1 kernel on the same tile and chunks"""
+    tile, H, W, win, mind, maxd, cons = CASES[name]
+    XG, DG, JC = F.PIPE_TILES[tile]
+    p = dict(winSize=win, maxDisparity=maxd, minDisparity=mind, gammaC=5.0, gammaP=17.5)
+    return ((F.also(F.pipe_tile(XG, DG, JC, static=static), n_chunks=1), W, H, p),
+            (F.workgroup_tile("%d,%d,%d,8" % (XG, DG, JC), win=win, SSAMD_ASW_STATIC=str(static)), W, H, p))
+
+
+def forced_rows():
+    return [row for name, static in PARAMS for row in _forms(name, static)]
 
 
 @pytest.fixture(scope="module")
@@ -51,32 +64,13 @@ def _images(H, W, seed):
 
 @pytest.mark.parametrize("name,static", PARAMS)
 def test_pipe_build_equals_the_round1_kernel(name, static, ss):
-    XG, DG, JC, H, W, win, mind, maxd, cons = CASES[name]
-    nD = maxd - mind + 1
-    m = ss.passive.StereoASW(winSize=win, maxDisparity=maxd, minDisparity=mind, consistent=cons, exact=False, gammaC=5.0, gammaP=17.5)
-
-    def costs(L, R):
-        c = np.empty((H, W, nD), np.float32)
-        _native.check(_native.lib().ssamd_asw_costs(L.ctypes.data, R.ctypes.data, H, W, win, maxd, mind, m.gammaC, m.gammaP, c.ctypes.data, -1))
-        return c
-    try:
-        for label, L, R in _images(H, W, 11):
-            _native.set_option("SSAMD_ASW_WAVE", "0")
-            _native.set_option("SSAMD_ASW_GEOM", "%d,%d" % (XG, DG))
-            _native.set_option("SSAMD_ASW_PIPE", str(JC))
-            _native.set_option("SSAMD_ASW_STATIC", str(static))
-            form, geom = _native.asw_kernel_form(W, H, win, maxd, mind), _native.asw_geometry(W, H, win, maxd, mind)
-            assert form["phase_shifted"] == 1 and form["chunk_columns"] == JC and form["wave_kernel"] == 0, form
-            assert geom["tile_x"] == 8 * XG and geom["chunk_d"] == 4 * DG and geom["n_chunks"] == 1, geom
-            got, got_c = m.compute(L, R), costs(L, R)
-            _native.set_option("SSAMD_ASW_GEOM", "%d,%d,%d,8" % (XG, DG, JC))      # same tile and chunks, round-1 kernel
-            _native.set_option("SSAMD_ASW_PIPE", "0")
-            assert _native.asw_kernel_form(W, H, win, maxd, mind)["phase_shifted"] == 0
-            want, want_c = m.compute(L, R), costs(L, R)
-            assert np.array_equal(got, want), (name, static, label, int((got != want).sum()))
-            nan = np.isnan(want_c)                  # (candidates the reference does not evaluate)
-            differ = (got_c.view(np.uint32) != want_c.view(np.uint32)) & ~nan
-            assert np.array_equal(np.isnan(got_c), nan) and not differ.any(), (name, static, label, int(differ.sum()))
-    finally:
-        for k in HOOKS:
-            _native.set_option(k, None)
+    pipe, round1 = _forms(name, static)
+    _, W, H, p = pipe
+    m = ss.passive.StereoASW(consistent=CASES[name][-1], exact=False, **p)
+    for label, L, R in _images(H, W, 11):
+        with F.forced(*pipe):
+            got, got_c = m.compute(L, R), F.cost_dump(L, R, p)
+        with F.forced(*round1):
+            want, want_c = m.compute(L, R), F.cost_dump(L, R, p)
+        assert np.array_equal(got, want), (name, static, label, int((got != want).sum()))
+        assert F.same_costs(got_c, want_c) == 0, (name, static, label, F.same_costs(got_c, want_c))

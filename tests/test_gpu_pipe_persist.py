@@ -10,18 +10,30 @@ import numpy as np
 import pytest
 from simplestereo_amd import _native
 
+import _asw_forms as F
+
 pytestmark = pytest.mark.gpu
 
-HOOKS = ("SSAMD_ASW_GEOM", "SSAMD_ASW_PIPE", "SSAMD_ASW_WAVE", "SSAMD_ASW_PERSIST")
 WORKERS = (1, 5, 16)
 
-# name -> XG, DG, JC (tile of 8 XG columns x 4 DG disparities, tap-column chunks), H, W, win, minD, maxD, consistent, tiles, disparity chunks
+# name -> tile (_asw_forms.PIPE_TILES: 8 XG columns x 4 DG disparities, tap-column chunks), H, W, win, minD, maxD, consistent, tiles, disparity chunks
 CASES = {
-    "120x196-3-tiles": (15, 49, 16, 40, 250, 35, 0, 192, False, 3, 1),       # nx & 7 != 0: no tile remap; partial last tile
-    "120x196-8-tiles": (15, 49, 16, 12, 960, 35, 0, 192, False, 8, 1),       # the remap branch
-    "generic-merging": (6, 9, 8, 24, 100, 35, 0, 35, True, 3, 1),            # keys, atomicMin, right-referenced pass
-    "two-chunks": (15, 25, 16, 16, 250, 35, 0, 192, False, 3, 2),            # the disparity chunk comes from the item
+    "120x196-3-tiles": ("120x196", 40, 250, 35, 0, 192, False, 3, 1),        # nx & 7 != 0: no tile remap; partial last tile
+    "120x196-8-tiles": ("120x196", 12, 960, 35, 0, 192, False, 8, 1),        # the remap branch
+    "generic-merging": ("48x36", 24, 100, 35, 0, 35, True, 3, 1),            # keys, atomicMin, right-referenced pass
+    "two-chunks": ("120x100", 16, 250, 35, 0, 192, False, 3, 2),             # the disparity chunk comes from the item
 }
+
+
+def _form(name, persist):
+    """the case's tile with the persistent form forced to `persist` workers (0: the plain launch), as (form, W, H, params)"""
+    tile, H, W, win, mind, maxd, cons, tiles, chunks = CASES[name]
+    p = dict(winSize=win, maxDisparity=maxd, minDisparity=mind, gammaC=5.0, gammaP=17.5)
+    return F.also(F.pipe_tile(*F.PIPE_TILES[tile], persist=persist), grid_x=tiles, n_chunks=chunks), W, H, p
+
+
+def forced_rows():
+    return [_form(name, persist) for name in CASES for persist in (0,) + WORKERS]
 
 
 @pytest.fixture(scope="module")
@@ -38,49 +50,30 @@ def _images(H, W, seed=11):
     return rng.integers(0, 256, (H, W, 3), dtype=np.uint8), rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
 
 
-def _force(name, persist):
-    XG, DG, JC, H, W, win, mind, maxd, cons, tiles, chunks = CASES[name]
-    _native.set_option("SSAMD_ASW_WAVE", "0")
-    _native.set_option("SSAMD_ASW_GEOM", "%d,%d" % (XG, DG))
-    _native.set_option("SSAMD_ASW_PIPE", str(JC))
-    _native.set_option("SSAMD_ASW_PERSIST", str(persist))
-    form, geom = _native.asw_kernel_form(W, H, win, maxd, mind), _native.asw_geometry(W, H, win, maxd, mind)
-    assert form["phase_shifted"] == 1 and form["chunk_columns"] == JC and form["wave_kernel"] == 0, form
-    assert geom["tile_x"] == 8 * XG and geom["chunk_d"] == 4 * DG and geom["grid_x"] == tiles and geom["n_chunks"] == chunks, geom
-
-
-def _unforce():
-    for k in HOOKS:
-        _native.set_option(k, None)
-
-
 def _run(ss, name, persist, exact=False):
     """(map, raw costs) of the case with the form forced to `persist`; with a worker count, the finished-item counter is checked
     behind each of the two launches"""
-    XG, DG, JC, H, W, win, mind, maxd, cons, tiles, chunks = CASES[name]
+    tile, H, W, win, mind, maxd, cons, tiles, chunks = CASES[name]
     L, R = _images(H, W)
-    m = ss.passive.StereoASW(winSize=win, maxDisparity=maxd, minDisparity=mind, consistent=cons, exact=exact, gammaC=5.0, gammaP=17.5)
-    costs = np.empty((H, W, maxd - mind + 1), np.float32)
-    try:
-        # first other images through the plain launch: the context's device buffers (map, keys, cost volume) are reused from call to
-        # call, and a tile the launch under test missed must not find an earlier run's correct values there
-        _force(name, 0)
+    p = _form(name, 0)[3]
+    m = ss.passive.StereoASW(consistent=cons, exact=exact, **p)
+    # first other images through the plain launch: the context's device buffers (map, keys, cost volume) are reused from call to
+    # call, and a tile the launch under test missed must not find an earlier run's correct values there
+    with F.forced(*_form(name, 0)):
         L2, R2 = _images(H, W, seed=12)
         m.compute(L2, R2)
-        _native.check(_native.lib().ssamd_asw_costs(L2.ctypes.data, R2.ctypes.data, H, W, win, maxd, mind, m.gammaC, m.gammaP, costs.ctypes.data, -1))
-        costs.fill(np.float32(-3.0))
-        _force(name, persist)
-        n0, l0 = _native.counter("pipe_persist_items"), _native.counter("pipe_persist_launches")
-        disp = m.compute(L, R)
-        n1, l1 = _native.counter("pipe_persist_items"), _native.counter("pipe_persist_launches")
-        _native.check(_native.lib().ssamd_asw_costs(L.ctypes.data, R.ctypes.data, H, W, win, maxd, mind, m.gammaC, m.gammaP, costs.ctypes.data, -1))
-        n2, l2 = _native.counter("pipe_persist_items"), _native.counter("pipe_persist_launches")
+        F.cost_dump(L2, R2, p)
+    grown = []
+    with F.forced(*_form(name, persist)):
+        for launch in (lambda: m.compute(L, R), lambda: F.cost_dump(L, R, p)):
+            with F.counted("pipe_persist_items") as n, F.counted("pipe_persist_launches") as ln:
+                out = launch()
+            grown += [out, (n.delta, ln.delta)]
         entries = _native.counter("exact_entries") if exact else None
-    finally:
-        _unforce()
+    disp, first, costs, second = grown
     items = tiles * H * chunks
     want = (items, 1) if persist else (0, 0)
-    assert (n1 - n0, l1 - l0) == want and (n2 - n1, l2 - l1) == want, (name, persist, items, n0, n1, n2, l0, l1, l2)
+    assert first == want and second == want, (name, persist, items, first, second)
     return disp, costs, entries
 
 
@@ -99,9 +92,7 @@ def test_persistent_form_equals_the_plain_launch(name, workers, ss):
     want, want_c, _ = _plain_run(ss, name)
     got, got_c, _ = _run(ss, name, workers)
     assert np.array_equal(got, want), (name, workers, int((got != want).sum()))
-    nan = np.isnan(want_c)                  # (candidates the reference does not evaluate)
-    differ = (got_c.view(np.uint32) != want_c.view(np.uint32)) & ~nan
-    assert np.array_equal(np.isnan(got_c), nan) and not differ.any(), (name, workers, int(differ.sum()))
+    assert F.same_costs(got_c, want_c) == 0, (name, workers, F.same_costs(got_c, want_c))
 
 
 @pytest.mark.parametrize("workers", WORKERS)
@@ -121,22 +112,18 @@ def test_two_row_ranges_with_the_persistent_form(workers, ss):
     its gap is the item's"""
     import torch
     name = "120x196-3-tiles"
-    XG, DG, JC, H, W, win, mind, maxd, cons, tiles, chunks = CASES[name]
+    tile, H, W, win, mind, maxd, cons, tiles, chunks = CASES[name]
     L, R = _images(H, W)
     tL, tR = torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda()
-    m = ss.passive.StereoASW(winSize=win, maxDisparity=maxd, minDisparity=mind, consistent=cons, exact=False, gammaC=5.0, gammaP=17.5)
+    m = ss.passive.StereoASW(consistent=cons, exact=False, **_form(name, 0)[3])
     row0, rows, skip0, nskip = 3, H - 7, 12, 13
     a, b = skip0 - row0, skip0 - row0 + nskip
-    try:
-        _force(name, 0)
+    with F.forced(*_form(name, 0)):
         want = m._compute_device(tL, tR, out_row0=row0, out_rows=rows)
-        _force(name, workers)
+    with F.forced(*_form(name, workers)):
         out = torch.full((rows, W), -7, dtype=torch.int16, device="cuda")
-        n0 = _native.counter("pipe_persist_items")
-        m._compute_device(tL, tR, out_row0=row0, out_rows=rows, out=out, skip=(skip0, nskip))
-        n1 = _native.counter("pipe_persist_items")
-    finally:
-        _unforce()
-    assert n1 - n0 == tiles * (rows - nskip) * chunks, (workers, n0, n1)
+        with F.counted("pipe_persist_items") as n:
+            m._compute_device(tL, tR, out_row0=row0, out_rows=rows, out=out, skip=(skip0, nskip))
+    assert n.delta == tiles * (rows - nskip) * chunks, (workers, n.delta)
     assert torch.equal(out[:a], want[:a]) and torch.equal(out[b:], want[b:]), workers
     assert bool((out[a:b] == -7).all()), "rows between the two ranges were written"
