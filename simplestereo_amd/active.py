@@ -1626,13 +1626,19 @@ def _periods(periods):
 
 
 def _mod_thr2(min_modulation):
-    """``sqrt(a^2 + b^2) / 2 < m`` on integers ``a``, ``b`` is ``a^2 + b^2 < ceil(4 m^2)``"""
+    """The threshold of the mask: a set masks its pixel iff ``a^2 + b^2 < 4 m^2`` in exact arithmetic on the double ``m``, which on
+    integers ``a``, ``b`` is ``a^2 + b^2 < min(ceil(4 m^2), 130051)``; ``inf`` -> 130051 (masks all), ``None`` -> 0 (masks none).
+    Integers throughout: ``m = p / q`` exactly (``float.as_integer_ratio``), so nothing is rounded -- ``ceil(4.0 * m * m)`` in
+    double is one off at about 6 % of the ``m`` next to a ``sqrt(s) / 2`` and 0 for every ``0 < m < 1e-162``."""
     if min_modulation is None:
         return 0
     m = _number(min_modulation, "min_modulation")
     if not m >= 0:
         raise ValueError("min_modulation must be a number >= 0 or None")
-    return int(min(math.ceil(min(4.0 * m * m, float(_MOD_THR2_ALL))), _MOD_THR2_ALL))
+    if m >= 181.0:                          # 4 * 181^2 > 130051 (and inf has no ratio)
+        return _MOD_THR2_ALL
+    p, q = m.as_integer_ratio()
+    return min(-((-4 * p * p) // (q * q)), _MOD_THR2_ALL)
 
 
 def phaseShiftPattern(periods, projRes):
@@ -1693,7 +1699,10 @@ def phaseShiftDecode(images, periods, projRes, maps=None, roi=None, min_modulati
     ``px = width * phi_x / (2 pi)`` and ``py = height * phi_y / (2 pi)``: as ``getProjCoord`` scales by the projector's
     resolution, not by the first period, the coordinates are pixels only when ``periods[v][0]`` equals the projector's extent
     along that axis (the reference's behaviour; nothing is raised otherwise).  fp64, the reference's operations in its order;
-    ``arctan2`` is the device library's, so the result is close to numpy's, not bit-equal.
+    ``arctan2`` is the device library's, so the result is close to numpy's, not bit-equal.  At an exact tie of a heterodyne
+    step, ``phi * T0 / T - theta`` an odd multiple of ``pi`` -- clean fringes never meet one, unstructured input (noise) does at
+    about one pixel in 10 000 --, ``k`` depends on the last bit of ``arctan2``, and the result may differ from numpy's by one
+    period ``T`` of that step, as numpy's does from the same chain in long double.
 
     Parameters
     ----------
@@ -1710,7 +1719,10 @@ def phaseShiftDecode(images, periods, projRes, maps=None, roi=None, min_modulati
         The region ``[y, y + height) x [x, x + width)``.  Default: the whole image.
     min_modulation : number >= 0, optional
         A pixel for which any set has ``sqrt((I3 - I1)^2 + (I0 - I2)^2) / 2 < min_modulation`` becomes (NaN, NaN).  The
-        test is made on integers, ``a^2 + b^2 < ceil(4 m^2)``.  Default None: no pixel is masked, as in the reference.
+        rule is exact: with ``a = I3 - I1``, ``b = I0 - I2`` and ``m`` the double passed, taken as the real number it is, a
+        set masks its pixel iff ``a^2 + b^2 < 4 m^2`` -- nothing is rounded, neither a square root nor ``4 m^2``.  The kernel
+        compares integers, ``a^2 + b^2 < min(ceil(4 m^2), 130051)`` with the ceiling taken on rationals (``inf`` masks every
+        pixel, any ``m > 0`` masks ``a = b = 0``).  Default None: no pixel is masked, as in the reference.
 
     Returns
     -------
@@ -1745,7 +1757,11 @@ class PhaseShift:
     periods : (list_x, list_y)
         As :func:`phaseShiftDecode` takes them.
     min_modulation : number >= 0, optional
-        As :func:`phaseShiftDecode` takes it.  Default None.
+        As :func:`phaseShiftDecode` takes it: a set masks its pixel iff ``a^2 + b^2 < 4 m^2`` exactly, ``m`` the double as
+        the real number it is.  Default None.
+
+    At an exact tie of a heterodyne step, which only unstructured input produces, the decoded coordinate (and so the point)
+    may lie one period of that step from numpy's: see :func:`phaseShiftDecode`.
     """
 
     def __init__(self, rig, periods, min_modulation=None):

@@ -5,7 +5,9 @@
 The triangulation is the per-point function the FTP and Gray-code clouds end with (tests/_ftp_cloud_ref.py,
 tests/_graycode_ref.py) on points that carry no half-pixel offset."""
 import json
+import math
 import os
+from fractions import Fraction
 
 import numpy as np
 
@@ -18,11 +20,34 @@ MOD_ALL = 2 * 255 * 255 + 1
 
 
 # ------------------------------------------------------------------------------------------------ the decode
+def masks(s, min_modulation):
+    """The rule itself, on one pair: a set with a^2 + b^2 = s masks its pixel iff s < 4 m^2, m the double as the rational it is"""
+    if min_modulation is None:
+        return False
+    m = float(min_modulation)
+    return True if m == np.inf else Fraction(int(s)) < 4 * Fraction(m) ** 2
+
+
 def mod_thr2(min_modulation):
-    """sqrt(a^2 + b^2) / 2 < m on integers a, b  <=>  a^2 + b^2 < ceil(4 m^2)"""
+    """The threshold t the kernel compares with, a^2 + b^2 < t: the smallest integer t in 0 .. MOD_ALL with t >= 4 m^2 (MOD_ALL if
+    there is none: above every a^2 + b^2 of 8-bit images), found by bisection on rationals -- no ceil, no float product"""
     if min_modulation is None:
         return 0
-    return int(min(np.ceil(min(4.0 * float(min_modulation) * float(min_modulation), float(MOD_ALL))), MOD_ALL))
+    m = float(min_modulation)
+    if not m >= 0:
+        raise ValueError(min_modulation)
+    if m == np.inf:
+        return MOD_ALL
+    want = 4 * Fraction(m) ** 2
+    num, den = want.numerator, want.denominator
+    lo, hi = 0, MOD_ALL                                    # the answer is in [lo, hi]
+    while lo < hi:
+        mid = (lo + hi) // 2
+        if mid * den >= num:                               # Fraction(mid) >= want, without building 17 Fractions per call
+            hi = mid
+        else:
+            lo = mid + 1
+    return lo
 
 
 def decode(stack, periods, proj_res, thr2=0, dtype=np.float64, details=False):
@@ -158,6 +183,106 @@ def scene(seed, res1, res2, periods, amplitude=100, low=2, extra=1):
 
 def same_bits(got, want):
     return G.same_points(got, want)
+
+
+# ------------------------------------------------------------------------------------------------ the whole input domain, and noise
+DOMAIN_JSON = os.path.join(GOLDEN, "phaseshift_domain_cases.json")
+DOMAIN_N = 511                                        # a = I3 - I1 and b = I0 - I2 are integers in -255 .. 255
+DOMAIN_PERIODS = [[64.0], [32.0]]                     # one period per axis: the result is extent * theta / (2 pi), no heterodyne step
+BAND = 1e-9                                           # a step with |kk - rint(kk)| > 0.5 - BAND sits on a tie of its k
+NOISE_SHAPE = (256, 1024)                             # 256 workgroups
+NOISE_PROJ = (1920, 1080)
+NOISE_PERIODS = {
+    "readme": [[1920.0, 240.0, 30.0], [1080.0, 135.0, 15.0]],
+    "small": [[64.0, 16.0, 4.0], [32.0, 8.0]],
+    "ratios": [[70.0, 9.5, 1.3], [33.0, 7.25]],                                     # T0 / T no integer
+    "eight": [[64.0 / (i + 1) for i in range(8)], [32.0 / (i + 1) for i in range(8)]],
+}
+
+
+def domain_pairs():
+    """int64 [511, 511] each: (a, b) of the x-set at pixel (row, col), a = row - 255 and b = col - 255; the y-set holds (b, a)"""
+    a, b = np.mgrid[0:DOMAIN_N, 0:DOMAIN_N].astype(np.int64) - 255
+    return a, b
+
+
+def domain_stack(lifted=False):
+    """uint8 [8, 511, 511]: every pair (a, b) of the decode's input domain once per axis.  x-set (planes I0 .. I3): I3 = max(a, 0),
+    I1 = max(-a, 0), I0 = max(b, 0), I2 = max(-b, 0); y-set: the transposed grid, so every pixel carries two different pairs.
+    lifted: the same differences at the top of the range, I3 = 255 - max(-a, 0), I1 = 255 - max(a, 0), ...: other bytes, the
+    same integers."""
+    a, b = domain_pairs()
+
+    def four(a, b):
+        z = np.zeros_like(a)
+        lo = [np.maximum(b, z), np.maximum(-a, z), np.maximum(-b, z), np.maximum(a, z)]           # I0, I1, I2, I3
+        return [255 - lo[(i + 2) % 4] for i in range(4)] if lifted else lo
+
+    stack = np.stack(four(a, b) + four(a.T, b.T))
+    assert stack.min() >= 0 and stack.max() <= 255
+    I = stack.astype(np.int64)
+    assert np.array_equal(I[3] - I[1], a) and np.array_equal(I[0] - I[2], b) and np.array_equal(I[7] - I[5], b) and np.array_equal(I[4] - I[6], a)
+    return stack.astype(np.uint8)
+
+
+def noise_stack(seed, periods):
+    """uint8 [4 (nx + ny), 256, 1024] of uniform noise"""
+    n = 4 * (len(periods[0]) + len(periods[1]))
+    return np.random.default_rng(seed).integers(0, 256, (n,) + NOISE_SHAPE, dtype=np.uint8)
+
+
+def candidates(a, b, periods, extent, band=BAND):
+    """What one axis of one pixel may decode to: the float64 restatement on the integers a[j], b[j] of its sets (arrays [n], n the
+    number of periods), written out on scalars, where every heterodyne step with |kk - rint(kk)| > 0.5 - band branches into
+    floor(kk) and ceil(kk) and every other step takes rint(kk) -> a list of floats, the restatement's own value among them.  The
+    angles come from the array call decode() makes."""
+    two_pi = 2.0 * np.pi
+    theta = [float(t) for t in np.mod(np.arctan2(np.asarray(a, np.float64), np.asarray(b, np.float64)), two_pi)]
+    T = [float(t) for t in periods]
+    phases = [theta[0]]
+    for j in range(1, len(T)):
+        step = []
+        for phase in phases:
+            kk = (phase * T[0] / T[j] - theta[j]) / two_pi
+            k = float(np.rint(kk))
+            for k in ((float(math.floor(kk)), float(math.ceil(kk))) if abs(kk - k) > 0.5 - band else (k,)):
+                step.append((theta[j] + two_pi * k) * T[j] / T[0])
+        phases = step
+    return [float(extent) * phase / two_pi for phase in phases]
+
+
+def pixel_candidates(stack, periods, proj_res, y, x, band=BAND):
+    """(candidates of px, candidates of py) of pixel (y, x) of the stack"""
+    out, i = [], 0
+    for v in range(2):
+        n = len(periods[v])
+        I = np.asarray(stack[i:i + 4 * n, y, x]).astype(np.int64).reshape(n, 4)
+        i += 4 * n
+        out.append(candidates(I[:, 3] - I[:, 1], I[:, 0] - I[:, 2], periods[v], proj_res[v], band))
+    return out
+
+
+def distance_to_candidates(got, stack, periods, proj_res, flagged, band=BAND):
+    """float [n, 2]: per flagged pixel (rows of np.argwhere(flagged)) and axis the distance of got [H, W, 2] to the nearest
+    candidate, and the largest candidate set met"""
+    at = np.argwhere(flagged)
+    dist, largest = np.zeros((len(at), 2)), 0
+    for i, (y, x) in enumerate(at):
+        for v, cand in enumerate(pixel_candidates(stack, periods, proj_res, y, x, band)):
+            dist[i, v] = min(abs(np.longdouble(got[y, x, v]) - np.longdouble(c)) for c in cand)
+            largest = max(largest, len(cand))
+    return dist, largest
+
+
+_DOMAIN = []
+
+
+def load_domain():
+    """tests/golden/phaseshift_domain_cases.json, loaded once"""
+    if not _DOMAIN:
+        with open(DOMAIN_JSON) as f:
+            _DOMAIN.append(json.load(f))
+    return _DOMAIN[0]
 
 
 _LOADED = []
