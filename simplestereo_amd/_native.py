@@ -1,5 +1,5 @@
 """ctypes binding of libssamd.so (C ABI in include/ssamd.h, include/ssamd_active.h, include/ssamd_graycode.h,
-include/ssamd_ftp_mapping.h and include/ssamd_structured_light.h).
+include/ssamd_ftp_mapping.h, include/ssamd_structured_light.h and include/ssamd_graycode_stereo.h).
 
 This is the only place Python touches the native library.  There is no Python or
 CPU fallback for the operators: if the library is missing, or no HIP device is
@@ -25,6 +25,8 @@ ACTIVE_VERSION = 1         # SSAMD_ACTIVE_VERSION of include/ssamd_active.h, the
 GRAYCODE_VERSION = 1       # SSAMD_GRAYCODE_VERSION of include/ssamd_graycode.h, the third
 FTP_MAPPING_VERSION = 1    # SSAMD_FTP_MAPPING_VERSION of include/ssamd_ftp_mapping.h, the fourth
 SL_VERSION = 1             # SSAMD_SL_VERSION of include/ssamd_structured_light.h, the fifth
+GRAYCODE_STEREO_VERSION = 1    # SSAMD_GRAYCODE_STEREO_VERSION of include/ssamd_graycode_stereo.h, the sixth
+STEREO_LAST, STEREO_MEAN = 0, 1     # SSAMD_STEREO_LAST, SSAMD_STEREO_MEAN: its reduce modes
 GRAYCODE_BLOCK = 1024      # SSAMD_GRAYCODE_BLOCK: pixels per block of the decode counts and the offsets
 
 (K_LAB, K_ASW_AGG, K_ASW_FIN, K_GSW_AGG, K_GSW_FIN, K_REMAP, K_REPROJECT, K_ASW_ALT, K_ASW_EXACT, K_UNWRAP, K_FTP,
@@ -71,6 +73,10 @@ _SIGNATURES = (
     # include/ssamd_graycode.h (SSAMD_GRAYCODE_VERSION); tests/test_graycode_cpu.py holds these rows to that header
     ("piiipp" + 9 * "i" + "DipIi", "ssamd_graycode_cloud"),
     ("piiiiDppp", "ssamd_graycode_cloud_device"),
+    # include/ssamd_graycode_stereo.h (SSAMD_GRAYCODE_STEREO_VERSION); tests/test_graycode_stereo_cpu.py holds these rows to that header
+    (2 * "piiii" + "iiippi", "ssamd_graycode_stereo_match"),
+    (2 * "piiii" + "iiipppp", "ssamd_graycode_stereo_match_device"),
+    (2 * "piippiiii" + 7 * "i" + "DipIi", "ssamd_graycode_stereo_points"),
 ) + tuple((args + last, name + suffix) for args, name in (       # NAME(..., int device) and NAME_device(..., void *stream)
     ("piiidp", "ssamd_iir_unwrap"),
     ("plllddp", "ssamd_np_unwrap"),
@@ -88,6 +94,8 @@ _SIGNATURES = (
     # include/ssamd_structured_light.h (SSAMD_SL_VERSION); tests/test_phaseshift_cpu.py holds these rows to that header
     ("piiipp" + 6 * "i" + "DDiiip", "ssamd_phaseshift_decode"),
     ("ppliiiDp", "ssamd_sl_triangulate"),
+    ("piiDpp", "ssamd_graycode_stereo_cloud"),
+    ("pplDp", "ssamd_stereo_triangulate"),
 ) for last, suffix in (("i", ""), ("p", "_device")))
 _RETURN_STRING = ("ssamd_last_error", "ssamd_kernel_name")
 _CTYPES = {"i": ctypes.c_int, "l": ctypes.c_longlong, "d": ctypes.c_double, "f": ctypes.c_float, "p": ctypes.c_void_p,

@@ -623,22 +623,27 @@ def _triangulation_geometry(rig, rect1, rect2, common_inv):
     return g
 
 
-def _undistort_maps(rig):
-    """float32 (mapx, mapy) of ``cv2.undistort(img, K1, distCoeffs1)``: ``initUndistortRectifyMap(K1, D1, I, K1, res1)``"""
+def _undistort_maps(rig, which=1):
+    """float32 (mapx, mapy) of ``cv2.undistort(img, K1, distCoeffs1)``: ``initUndistortRectifyMap(K1, D1, I, K1, res1)`` -- with
+    ``which=2`` those of the rig's second camera (K2, D2, res2)"""
+    if which == 2:
+        return _init_undistort_rectify_map(rig.intrinsic2, rig.distCoeffs2, np.eye(3), rig.intrinsic2, rig.res2)
     return _init_undistort_rectify_map(rig.intrinsic1, rig.distCoeffs1, np.eye(3), rig.intrinsic1, rig.res1)
 
 
-def _cached_maps(cache, rig, device=None):
-    """The float32 (mapx, mapy) of ``cv2.undistort`` of a rig's camera, on the host (``device`` None) or as tensors on a device,
-    built on first use and kept in ``cache``, the dict ``StereoFTP``, ``GrayCode`` and ``StructuredLightRig`` hold per instance."""
-    if "host" not in cache:
-        cache["host"] = _undistort_maps(rig)
+def _cached_maps(cache, rig, device=None, which=1):
+    """The float32 (mapx, mapy) of ``cv2.undistort`` of a rig's camera (``which``: 1 or 2), on the host (``device`` None) or as tensors
+    on a device, built on first use and kept in ``cache``, the dict ``StereoFTP``, ``GrayCode``, ``GrayCodeStereo`` and
+    ``StructuredLightRig`` hold per instance."""
+    host, on = ("host", "maps ") if which == 1 else ("host %d" % which, "maps %d " % which)
+    if host not in cache:
+        cache[host] = _undistort_maps(rig, which)
     if device is None:
-        return cache["host"]
-    if "maps " + str(device) not in cache:
+        return cache[host]
+    if on + str(device) not in cache:
         import torch
-        cache["maps " + str(device)] = tuple(torch.from_numpy(m).to(device) for m in cache["host"])
-    return cache["maps " + str(device)]
+        cache[on + str(device)] = tuple(torch.from_numpy(m).to(device) for m in cache[host])
+    return cache[on + str(device)]
 
 
 def _undistort_device(cache, rig, img):

@@ -29,6 +29,10 @@ heterodyne unwrapping (``PhaseShift``).  No cv2 call anywhere.
     points = ss.active.GrayCode(rig).getCloud(images)                   # float64 (n, 1, 3); images uint8 [N, H, W] or paths
     proj = ss.active.grayCodeDecode(images, rig.res2, white_thr=5)      # int32 [H, W, 2]: (xDec, yDec) or (-1, -1)
 
+    points = ss.active.GrayCodeStereo(rig2cam, projRes).getCloud((stack1, stack2))  # float64 (n, 1, 3): two cameras, one projector
+    pairs = ss.active.grayCodeMatch(proj1, proj2, projRes, reduce="mean")           # float64 [Hp, Wp, 4]: (x1, y1, x2, y2) or NaN
+    points = ss.active.stereoTriangulate(rig2cam, points1, points2)                 # float64 (n, 1, 3): any camera-camera couples
+
     patterns = ss.active.phaseShiftPattern(periods, rig.res2)           # uint8 [4 (nx + ny), Hp, Wp]
     cloud = ss.active.PhaseShift(rig, periods).getCloud(images)         # float64 [H, W, 3], NaN where masked
     proj = ss.active.phaseShiftDecode(images, periods, rig.res2)        # float64 [H, W, 2]: (px, py)
@@ -80,6 +84,18 @@ parity with cv2 itself is pinned only where ``cv2.structured_light`` is installe
 ``GrayCodeDouble`` stays out: the reference's version cannot run (it indexes a projector-shaped array with camera coordinates,
 adds 0.5 to an integer array in place and uses a ``self.R_inv`` it never defines); ``grayCodeDecode`` of the two cameras' stacks
 is the piece to write one's own from.
+
+``GrayCodeStereo`` is what that class sets out to do -- conventional active stereo, two calibrated cameras and one uncalibrated
+projector (``active.py:1463-1608``; C ABI in ``include/ssamd_graycode_stereo.h``) -- under a name of its own, since it is no
+drop-in for code that never ran.  Its loops are kept, with the indices the right way round: each camera's stack is decoded
+(``grayCodeDecode``, the maps of ``cv2.undistort(img, K_i, distCoeffs_i)`` fused in), each camera's decoded map is inverted into a
+projector-shaped table (``graycode_scatter_kernel``: a scatter with integer atomics, ``reduce="last"`` the reference's
+overwriting loop as an atomic max on the raster index, ``reduce="mean"`` the exact centroid from 64-bit integer sums), a projector
+pixel seen by BOTH cameras gives a couple of pixel centres (``graycode_match_kernel``; ``grayCodeMatch`` is scatter and match on
+their own), and the couples are triangulated camera against camera (``graycode_stereo_cloud_kernel``: ``Rectify1``, ``Rectify2``,
+``baseline * (p1 / |disparity|)``, the common rotation undone, ``active.py:1594-1606`` -- the end of ``ftpCloud``'s triangulation,
+by the same device function, without ``undistortPoints``; ``stereoTriangulate`` is that step for couples of any origin).  No
+float atomics: every result is the same bytes on every run.  A couple with zero disparity gives inf / NaN, as in the reference.
 
 ``PhaseShift`` is phase shifting with heterodyne unwrapping [Reich 1997], the third decoding method of the reference, which
 writes it out in ``calibration.phaseShift`` (``calibration.py:656-687`` and ``:726-738``; C ABI in
@@ -192,6 +208,31 @@ non-empty region reaching outside the image
 PIL absent: ``generateGrayCodeImgs``, a list of paths      ``ImportError``
 =========================================================  =======================
 
+``grayCodeMatch``, ``stereoTriangulate``, ``GrayCodeStereo`` and ``GrayCodeStereo.getCloud`` (each stack, ``white_thr`` and each
+``roi`` as in the table above):
+
+=========================================================  =======================
+condition                                                  exception
+=========================================================  =======================
+``projRes`` not two integers in 1 .. 65536, or of 2^31     ``ValueError``
+pixels or more
+``reduce`` neither ``"last"`` nor ``"mean"``               ``ValueError``
+a decoded map neither ndarray nor CUDA/HIP tensor, or not  ``TypeError``
+int32
+a decoded map not [h, w, 2]                                ``ValueError``
+an origin not two integers >= 0; a map of 2^31 pixels or   ``ValueError``
+more, or reaching that far from the origin
+one input on the host and one on a device, or on two       ``TypeError``
+devices (maps, points, stacks)
+``rig`` not a ``StereoRig``                                ``ValueError("Invalid argument!")``
+points neither ndarray nor tensor, or not of a real dtype  ``TypeError``
+points whose last dimension is not 2, or of two counts     ``ValueError``
+a rig whose geometry is not finite                         ``ValueError``
+``images`` neither (stack1, stack2) nor a sequence of      ``TypeError``
+(path1, path2) couples
+``getCloud``: an image not of ``res1`` / ``res2``          ``ValueError("Image size of {name or index} is mismatch!")``
+=========================================================  =======================
+
 ``phaseShiftPattern``, ``phaseShiftDecode``, ``PhaseShift`` and ``PhaseShift.getCloud`` (images, maps and the resolution as in the
 table above):
 
@@ -221,7 +262,7 @@ import os
 import numpy as np
 
 from . import _native
-from ._rigs import (INTER_LINEAR, NGEOM, StructuredLightRig, _cached_maps, _dist_vector, _distort, _low_level_rectify, _r_inv4, _remap,
+from ._rigs import (INTER_LINEAR, NGEOM, StereoRig, StructuredLightRig, _cached_maps, _dist_vector, _distort, _low_level_rectify, _r_inv4, _remap,
                     _triangulation_geom, _triangulation_geometry, _undistort_device, _undistort_points)
 from ._native import c_double as _c_double, is_device_tensor as _is_device_tensor
 
@@ -229,7 +270,7 @@ __all__ = ["ftpPhase", "ftpCloud", "ftpFringeOrder", "ftpGeometry", "FtpGeometry
            "findCentralStripe", "buildFringe", "StereoFTP", "grayCodePattern", "generateGrayCodeImgs", "grayCodeDecode", "GrayCode",
            "GrayCodeSingle", "MAX_PROJECTOR", "ftpCarrierPhase", "ftpStripePhase", "ftpMappingCloud", "ftpMappingGeometry",
            "FtpMappingGeometry", "StereoFTP_Mapping", "StereoFTP_PhaseOnly", "phaseShiftPattern", "phaseShiftDecode", "PhaseShift",
-           "MAX_PERIODS"]
+           "MAX_PERIODS", "grayCodeMatch", "stereoTriangulate", "GrayCodeStereo"]
 
 MAX_WIDTH = 8192          # SSAMD_FTP_MAX_W: twiddle table, gray rows and a chunk of bins of one row in 160 KiB of LDS
 MAX_PROJECTOR = 65536     # Gray code: at most 16 bits per projector axis, 64 pattern images
@@ -1468,6 +1509,25 @@ def grayCodeDecode(images, projRes, white_thr=5, maps=None, roi=None):
     return out
 
 
+def _gray_load(paths, count, size):
+    """The first ``count`` files as uint8 planes of ``size`` (the rules of :meth:`GrayCode._load`)"""
+    try:
+        from PIL import Image
+    except ImportError:
+        raise ImportError("reading image files needs PIL (the pillow package), which is not installed: pass arrays") from None
+    planes = []
+    for fname in paths[:count]:
+        with Image.open(fname) as im:
+            if im.mode != "L":
+                raise ValueError("%s is not an 8-bit single-channel image (mode %r): convert it yourself and pass arrays"
+                                 % (fname, im.mode))
+            img = np.array(im, dtype=np.uint8)
+        if (img.shape[1], img.shape[0]) != size:
+            raise ValueError("Image size of %s is mismatch!" % (fname,))
+        planes.append(img)
+    return planes
+
+
 class GrayCode:
     """
     Gray-code structured light with a calibrated camera-projector rig (the reference's ``GrayCode``, ``active.py:1130-1263``),
@@ -1509,21 +1569,7 @@ class GrayCode:
     def _load(self, paths, size):
         """The first ``num_patterns`` files as uint8 planes.  cv2's colour -> gray conversion is not restated: only 8-bit
         single-channel files are read."""
-        try:
-            from PIL import Image
-        except ImportError:
-            raise ImportError("reading image files needs PIL (the pillow package), which is not installed: pass arrays") from None
-        planes = []
-        for fname in paths[:self.num_patterns]:
-            with Image.open(fname) as im:
-                if im.mode != "L":
-                    raise ValueError("%s is not an 8-bit single-channel image (mode %r): convert it yourself and pass arrays"
-                                     % (fname, im.mode))
-                img = np.array(im, dtype=np.uint8)
-            if (img.shape[1], img.shape[0]) != size:
-                raise ValueError("Image size of %s is mismatch!" % (fname,))
-            planes.append(img)
-        return planes
+        return _gray_load(paths, self.num_patterns, size)
 
     def getCloud(self, images, roi=None, dense=False):
         """
@@ -1596,6 +1642,310 @@ class GrayCode:
 
 
 GrayCodeSingle = GrayCode
+
+
+# ------------------------------------------------------------------------------------------------ Gray code, two cameras
+_REDUCE = {"last": _native.STEREO_LAST, "mean": _native.STEREO_MEAN}
+
+
+def _reduce_mode(reduce):
+    if not isinstance(reduce, str) or reduce not in _REDUCE:
+        raise ValueError('reduce must be "last" or "mean"')
+    return _REDUCE[reduce]
+
+
+def _stereo_proj(projRes):
+    """-> (width, height, ncol, nrow) of a projector whose table the two-camera match can index: fewer than 2^31 pixels"""
+    proj = _proj_res(projRes)
+    if proj[0] * proj[1] >= 1 << 31:
+        raise ValueError("a projector of %d x %d pixels is not supported: 2^31 or more" % (proj[0], proj[1]))
+    return proj
+
+
+def _origin(origin, name):
+    try:
+        vals = tuple(origin)
+    except TypeError:
+        vals = ()
+    if len(vals) != 2 or not all(_integer(v) for v in vals) or min(int(v) for v in vals) < 0:
+        raise ValueError("%s must be (x, y), two integers that are not negative" % name)
+    return int(vals[0]), int(vals[1])
+
+
+def _decoded_map(d, name):
+    """-> (contiguous, 16-byte aligned int32 [h, w, 2] where it is, is it on a device)"""
+    dev = _is_device_tensor(d)
+    if not (dev or isinstance(d, np.ndarray)):
+        raise TypeError("%s must be an int32 ndarray or CUDA/HIP tensor" % name)
+    if dev:
+        import torch
+        if d.dtype != torch.int32:
+            raise TypeError("%s must be int32" % name)
+    elif d.dtype != np.int32:
+        raise TypeError("%s must be int32" % name)
+    if d.ndim != 3 or int(d.shape[2]) != 2:
+        raise ValueError("%s must be [h, w, 2]: the result of grayCodeDecode" % name)
+    if dev:
+        d = d.contiguous()
+        return (d.clone() if d.data_ptr() & 15 else d), True
+    return np.ascontiguousarray(d), False
+
+
+def _match_box(d, origin):
+    """(x0, y0, w, h) of a decoded map at ``origin``, checked against the limits of the match"""
+    h, w = int(d.shape[0]), int(d.shape[1])
+    if h * w >= 1 << 31 or (origin[1] + h) * (origin[0] + w) >= 1 << 31:
+        raise ValueError("decoded maps of 2^31 pixels or more, or reaching that far from the image origin, are not supported")
+    return origin[0], origin[1], w, h
+
+
+def _match_args(d1, box1, d2, box2, proj, mode):
+    return (_ptr(d1), box1[3], box1[2], box1[0], box1[1], _ptr(d2), box2[3], box2[2], box2[0], box2[1], proj[0], proj[1], mode)
+
+
+def _gray_match(d1, box1, d2, box2, proj, mode, dev):
+    """-> (matches float64 [Hp, Wp, 4], matched cells per block int32 [nblocks]) where the decoded maps are"""
+    pw, ph = proj[0], proj[1]
+    args = _match_args(d1, box1, d2, box2, proj, mode)
+    nblocks = _gray_blocks(ph, pw)
+    if not dev:
+        matches, counts = np.empty((ph, pw, 4), np.float64), np.empty((nblocks,), np.int32)
+        _native.check(_native.lib().ssamd_graycode_stereo_match(*args, matches.ctypes.data, counts.ctypes.data, -1), _INVALID)
+        return matches, counts
+    import torch
+    matches = torch.empty((ph, pw, 4), dtype=torch.float64, device=d1.device)
+    counts = torch.empty((nblocks,), dtype=torch.int32, device=d1.device)
+    per_cell = 20 if mode == _native.STEREO_MEAN else 4
+    scratch = torch.empty((2 * ((per_cell * ph * pw + 7) // 8),), dtype=torch.int64, device=d1.device)    # SSAMD_GRAYCODE_STEREO_SCRATCH
+    lib = _native.lib()
+    with torch.cuda.device(d1.device):
+        rc = lib.ssamd_graycode_stereo_match_device(*args, matches.data_ptr(), counts.data_ptr(), scratch.data_ptr(),
+                                                    ctypes.c_void_p(torch.cuda.current_stream(d1.device).cuda_stream))
+        if rc:
+            _native.check(rc, _INVALID)
+    return matches, counts
+
+
+def grayCodeMatch(decoded1, decoded2, projRes, reduce="last", origin1=(0, 0), origin2=(0, 0)):
+    """
+    Two cameras' decoded Gray-code maps -> camera-camera correspondences, one per projector pixel: the inversion of both
+    camera -> projector maps, by HIP kernels (``graycode_scatter_kernel`` once per camera, ``graycode_match_kernel``).
+
+    Of the pixels of one camera that decode to one projector pixel, ``reduce="last"`` keeps the one that comes last in raster
+    order (the reference's loops, where a later pixel overwrites an earlier one) and ``reduce="mean"`` their centroid (exact
+    integer sums, one division): sub-pixel where the cameras out-resolve the projector.  Integer atomics only: the same bytes on
+    every run.
+
+    Parameters
+    ----------
+    decoded1, decoded2 : ndarray or CUDA/HIP tensor int32 ``[h, w, 2]``
+        What :func:`grayCodeDecode` returns for camera 1 and camera 2 (sizes may differ); both on the host or both on one
+        device.  ``(-1, -1)``, or a value outside the projector, contributes nothing.
+    projRes : (width, height)
+        Of the projector, each 1 .. 65536, fewer than 2^31 pixels together.
+    reduce : "last" or "mean", optional
+    origin1, origin2 : (x, y), optional
+        Where each map's first pixel lies in its camera image (the ``roi`` origin it was decoded with): the coordinates of
+        the result are absolute image coordinates.  Default (0, 0).
+
+    Returns
+    -------
+    ndarray or tensor
+        float64 ``[Hp, Wp, 4]``: ``(x1 + 0.5, y1 + 0.5, x2 + 0.5, y2 + 0.5)``, pixel centres, where both cameras see the projector
+        pixel, four NaN elsewhere.  Where the inputs are.
+    """
+    proj = _stereo_proj(projRes)
+    mode = _reduce_mode(reduce)
+    d1, dev1 = _decoded_map(decoded1, "decoded1")
+    d2, dev2 = _decoded_map(decoded2, "decoded2")
+    if dev1 != dev2 or (dev1 and d1.device != d2.device):
+        raise TypeError("decoded1 and decoded2 must both be on the host or both on one device")
+    box1, box2 = _match_box(d1, _origin(origin1, "origin1")), _match_box(d2, _origin(origin2, "origin2"))
+    return _gray_match(d1, box1, d2, box2, proj, mode, dev1)[0]
+
+
+def _stereo_geometry(rect1, rect2, common_inv, baseline):
+    """The ``SSAMD_FTP_CLOUD_NGEOM`` doubles of the two-camera triangulation: only ``[40:68]`` (the rectifying transforms, the
+    inverse common orientation, the baseline) are read; no intrinsics, no distortion -- both images were undistorted."""
+    g = np.zeros(NGEOM)
+    g[40:49] = np.asarray(rect1, dtype=np.float64).ravel()
+    g[49:58] = np.asarray(rect2, dtype=np.float64).ravel()
+    g[58:67] = np.asarray(common_inv, dtype=np.float64).ravel()
+    g[67] = baseline
+    if not np.isfinite(g).all():
+        raise ValueError("the rig gives a geometry that is not finite")
+    return g
+
+
+def _triangulate_pairs(geom, points1, points2):
+    pts = StructuredLightRig._points
+    p1, p2 = pts(points1, "points1"), pts(points2, "points2")
+    if _is_device_tensor(p1) != _is_device_tensor(p2) or (_is_device_tensor(p1) and p1.device != p2.device):
+        raise TypeError("points1 and points2 must both be on the host or both on one device")
+    if p1.shape[0] != p2.shape[0]:
+        raise ValueError("%d points of image 1 but %d of image 2" % (p1.shape[0], p2.shape[0]))
+    n = int(p1.shape[0])
+    gp = geom.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    return _native.run("ssamd_stereo_triangulate", (p1, p2), (n, 1, 3), lambda a, b, out: (a, b, n, gp, out), _INVALID)
+
+
+def stereoTriangulate(rig, points1, points2):
+    """
+    Triangulate camera-camera correspondences of a calibrated two-camera rig, by one HIP kernel
+    (``graycode_stereo_cloud_kernel`` on point pairs): the two-camera counterpart of ``StructuredLightRig.triangulate`` and the
+    last step of :meth:`GrayCodeStereo.getCloud` (reference ``active.py:1594-1606``), by the same device function
+    (``rectified_triangulate``), fp64: ``Rectify1`` on ``points1``, ``Rectify2`` on ``points2`` (only x is used),
+    ``getBaseline() * (p1 / |disparity|)`` and the common rotation undone.  No ``undistortPoints``: the points of BOTH images
+    must already be undistorted.  A disparity of exactly 0 gives inf / NaN coordinates, as the reference's arithmetic does.
+
+    Parameters
+    ----------
+    rig : StereoRig
+        Two calibrated cameras; anything else is ``ValueError("Invalid argument!")``.
+    points1, points2 : numpy.ndarray or CUDA/HIP tensor
+        Ordered corresponding (x, y) couples, of any real dtype; the last dimension must be 2.  Both on the host or both on
+        one device.  They are converted to float64.
+
+    Returns
+    -------
+    numpy.ndarray or tensor
+        float64 ``(n, 1, 3)``; three NaN where a couple holds a NaN.  Where the inputs are.
+    """
+    if isinstance(rig, StructuredLightRig):              # its R already is the common orientation
+        geom = _stereo_geometry(rig.R1, rig.R2, rig.R_inv[:3, :3], rig.getBaseline())
+    elif isinstance(rig, StereoRig):
+        rect1, rect2, common = _low_level_rectify(rig)
+        geom = _stereo_geometry(rect1, rect2, np.linalg.inv(common), rig.getBaseline())
+    else:
+        raise ValueError("Invalid argument!")
+    return _triangulate_pairs(geom, points1, points2)
+
+
+class GrayCodeStereo:
+    """
+    Gray-code active stereo with two calibrated cameras and one uncalibrated projector: what the reference's ``GrayCodeDouble``
+    (``active.py:1463-1608``) sets out to do, with no cv2 call.  It is not a drop-in for that class, which cannot run as published;
+    the semantics are those of its loops, repaired: both stacks are decoded (:func:`grayCodeDecode`, ``cv2.undistort`` of each
+    camera fused in), both camera -> projector maps are inverted into one projector-shaped table (:func:`grayCodeMatch`), and the
+    projector pixels both cameras see are triangulated camera against camera (:func:`stereoTriangulate`).  The projector is
+    only a source of codes: its calibration plays no part.
+
+    Parameters
+    ----------
+    rig : StereoRig
+        Two calibrated cameras.
+    projRes : (width, height)
+        Of the projector, each 1 .. 65536, fewer than 2^31 pixels together.
+    black_thr : int, optional
+        Stored; ``getProjPixel`` does not read it.  Default 40.
+    white_thr : int, optional
+        Minimum difference between a pattern image and its inverse for a valid pixel, 0 .. 256.  Default 5.
+    reduce : "last" or "mean", optional
+        Which camera pixel stands for a projector pixel that several decode to (:func:`grayCodeMatch`).  ``"last"``, the
+        default, is the reference's loop; ``"mean"`` is sub-pixel when the cameras out-resolve the projector.
+
+    The attributes are the reference's: ``rig``, ``projRes``, ``num_patterns``, ``Rectify1``, ``Rectify2`` -- and ``R_inv``
+    (4 x 4), which the reference reads but never assigns.  There is no ``graycode`` attribute.
+    """
+
+    def __init__(self, rig, projRes, black_thr=40, white_thr=5, reduce="last"):
+        if not isinstance(rig, StereoRig):
+            raise ValueError("Invalid argument!")
+        self.rig = rig
+        self._proj = _stereo_proj(projRes)
+        self.projRes = (self._proj[0], self._proj[1])
+        self.black_thr = black_thr
+        self.white_thr = _white_thr(white_thr)
+        self.reduce = reduce
+        self._mode = _reduce_mode(reduce)
+        self.num_patterns = 2 * (self._proj[2] + self._proj[3])
+        self.Rectify1, self.Rectify2, commonR = _low_level_rectify(rig)
+        self.R_inv = _r_inv4(commonR)
+        self._cache = {}                 # _cached_maps' entries, both cameras'
+
+    def _geometry(self):
+        return _stereo_geometry(self.Rectify1, self.Rectify2, self.R_inv[:3, :3], self.rig.getBaseline())
+
+    def _stacks(self, images):
+        """-> ((stack1, stack2), on a device) of ``(stack1, stack2)`` or of the reference's list of (pathL, pathR) couples"""
+        sizes = [(int(r[0]), int(r[1])) for r in (self.rig.res1, self.rig.res2)]
+        if not isinstance(images, (list, tuple)) or not len(images):
+            raise TypeError("images must be (stack1, stack2) or a sequence of (path1, path2) couples")
+        if all(isinstance(p, (list, tuple)) and len(p) == 2 and all(isinstance(q, (str, os.PathLike)) for q in p) for p in images):
+            images = [_gray_load([p[i] for p in images], self.num_patterns, sizes[i]) for i in range(2)]
+        elif len(images) != 2:
+            raise TypeError("images must be (stack1, stack2) or a sequence of (path1, path2) couples")
+        (s1, dev1), (s2, dev2) = (_gray_stack(images[i], sizes[i]) for i in range(2))
+        if dev1 != dev2 or (dev1 and s1.device != s2.device):
+            raise TypeError("the two stacks must both be on the host or both on one device")
+        return (s1, s2), dev1
+
+    def getCloud(self, images, roi1=None, roi2=None, dense=False):
+        """
+        The 3-D points of two cameras' sets of Gray-code images (what ``active.py:1508-1608`` sets out to compute).
+
+        Each stack is decoded over its roi through the maps of ``cv2.undistort(img, K_i, distCoeffs_i)``; each camera fills a
+        projector-shaped table (``reduce``); a projector pixel both cameras see gives the couple of pixel centres
+        ``(x1 + 0.5, y1 + 0.5)``, ``(x2 + 0.5, y2 + 0.5)`` in absolute image coordinates; the couples are triangulated in
+        projector raster order (:func:`stereoTriangulate`).  A couple whose rectified x coordinates coincide (zero disparity)
+        gives inf / NaN coordinates, as the reference's arithmetic does; nothing is raised.
+
+        Parameters
+        ----------
+        images : (stack1, stack2), or a sequence of (path1, path2) couples
+            Each stack as :func:`grayCodeDecode` takes it, of the rig's ``res1`` / ``res2``, both on the host or both on one
+            device; or the reference's list of couples of image paths (8-bit single-channel files, read with PIL), in the
+            order of the patterns.  Any following extra image is ignored.
+        roi1, roi2 : (x, y, x_end, y_end), optional
+            Per camera, read as :meth:`GrayCode.getCloud` reads its roi.  Default None: the whole image.
+        dense : bool, optional
+            ``True``: the cloud in the shape of the projector, NaN where a projector pixel is not seen by both cameras; with
+            tensors nothing is read back.  Default False: with tensors one integer, the number of points, is read back.
+
+        Returns
+        -------
+        ndarray or tensor
+            float64 ``(n, 1, 3)``, the points in projector raster order -- or ``[Hp, Wp, 3]`` with ``dense``.  Where the images are.
+        """
+        (s1, s2), dev = self._stacks(images)
+        stacks = (s1, s2)
+        boxes = [_gray_roi(roi, (int(r[0]), int(r[1]))) for roi, r in ((roi1, self.rig.res1), (roi2, self.rig.res2))]
+        geom = self._geometry()
+        pw, ph = self.projRes
+        maps = [_cached_maps(self._cache, self.rig, stacks[i].device if dev else None, which=i + 1) for i in range(2)]
+        args = [_gray_decode_args(stacks[i], self._proj, self.white_thr, maps[i][0], maps[i][1], boxes[i]) for i in range(2)]
+        if not all(b[2] * b[3] for b in boxes):                    # a camera without pixels: no projector pixel is seen by both
+            if dev:
+                import torch
+                return (torch.full((ph, pw, 3), float("nan"), dtype=torch.float64, device=s1.device) if dense
+                        else torch.empty((0, 1, 3), dtype=torch.float64, device=s1.device))
+            return np.full((ph, pw, 3), np.nan) if dense else np.empty((0, 1, 3), np.float64)
+        lib = _native.lib()
+        gp = geom.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        if not dev:
+            buf = np.empty((ph * pw, 3), np.float64)
+            n = ctypes.c_int(0)
+            side = [a[0:1] + a[2:10] for a in args]                # planes, hc, wc, mapx, mapy, x0, y0, h, w
+            _native.check(lib.ssamd_graycode_stereo_points(*side[0], *side[1], *args[0][1:2], *args[0][10:], self._mode, gp,
+                                                           1 if dense else 0, buf.ctypes.data, ctypes.byref(n), -1), _INVALID)
+            if dense:
+                return buf.reshape(ph, pw, 3)
+            return buf[:n.value].copy().reshape(-1, 1, 3)
+        import torch
+        decoded = [_gray_decode_device(stacks[i], args[i], boxes[i][3], boxes[i][2])[0] for i in range(2)]
+        matches, counts = _gray_match(decoded[0], boxes[0], decoded[1], boxes[1], self._proj, self._mode, True)
+        if dense:
+            out = torch.empty((ph, pw, 3), dtype=torch.float64, device=s1.device)
+            _native.call_on_stream(s1, lib.ssamd_graycode_stereo_cloud_device, matches.data_ptr(), pw, ph, gp, None, out.data_ptr(), invalid=_INVALID)
+            return out
+        offsets = torch.empty((counts.shape[0] + 1,), dtype=torch.int32, device=s1.device)
+        _native.call_on_stream(s1, lib.ssamd_graycode_offsets_device, counts.data_ptr(), int(counts.shape[0]), offsets.data_ptr(), invalid=_INVALID)
+        n = int(offsets[-1].item())                                # the one read-back: the number of points sizes the result
+        out = torch.empty((n, 1, 3), dtype=torch.float64, device=s1.device)
+        if n:
+            _native.call_on_stream(s1, lib.ssamd_graycode_stereo_cloud_device, matches.data_ptr(), pw, ph, gp, offsets.data_ptr(), out.data_ptr(),
+                                   invalid=_INVALID)
+        return out
 
 
 # ------------------------------------------------------------------------------------------------ phase shifting

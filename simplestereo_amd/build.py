@@ -18,7 +18,7 @@ def needs_build():
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    deps = _sources() + [os.path.join(os.path.dirname(_PKG), "include", h) for h in ("ssamd.h", "ssamd_active.h", "ssamd_graycode.h", "ssamd_ftp_mapping.h", "ssamd_structured_light.h")]
+    deps = _sources() + [os.path.join(os.path.dirname(_PKG), "include", h) for h in ("ssamd.h", "ssamd_active.h", "ssamd_graycode.h", "ssamd_ftp_mapping.h", "ssamd_structured_light.h", "ssamd_graycode_stereo.h")]
     return any(os.path.getmtime(s) > t for s in deps if os.path.exists(s))
 
 

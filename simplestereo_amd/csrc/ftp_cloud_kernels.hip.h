@@ -65,6 +65,23 @@ __device__ __forceinline__ void ftp_project(const Geom &G, double u, double v, d
     Ya = G.f2[1] * yd + G.f2[3];
 }
 
+// A point (u, v) of image 1 and an undistorted point (hx, hy) of image 2 -> point o[0..2]: the two rectifying homographies (of
+// the second point only x is used), disparity -> depth, the common rotation undone.  Reads R1, R2, Ri and baseline of G.  What
+// ftp_triangulate ends with, and all of the two-camera triangulation (graycode_stereo_kernels.hip.h, active.py:1594-1606), where
+// both images were undistorted beforehand.  A disparity of exactly 0 divides by zero as the reference's arithmetic does: inf / NaN.
+__device__ __forceinline__ void rectified_triangulate(const FtpCloudGeom &G, double u, double v, double hx, double hy, double *o)
+{
+#pragma clang fp contract(off)
+    const double ppx = ((G.R2[0] * hx + G.R2[1] * hy) + G.R2[2]) / ((G.R2[6] * hx + G.R2[7] * hy) + G.R2[8]);
+    const double Wc = (G.R1[6] * u + G.R1[7] * v) + G.R1[8];
+    const double pcx = ((G.R1[0] * u + G.R1[1] * v) + G.R1[2]) / Wc, pcy = ((G.R1[3] * u + G.R1[4] * v) + G.R1[5]) / Wc;
+    const double disparity = fabs(ppx - pcx);
+    const double px = G.baseline * (pcx / disparity), py = G.baseline * (pcy / disparity), pz = G.baseline * (1.0 / disparity);
+    o[0] = (G.Ri[0] * px + G.Ri[1] * py) + G.Ri[2] * pz;
+    o[1] = (G.Ri[3] * px + G.Ri[4] * py) + G.Ri[5] * pz;
+    o[2] = (G.Ri[6] * px + G.Ri[7] * py) + G.Ri[8] * pz;
+}
+
 // The camera pixel centre (u, v) and the projector point (Xh, Yh) it corresponds to -> point o[0..2]: the triangulation both
 // structured-light methods end with (active.py:813-841 for StereoFTP, :1246-1261 for GrayCode), the operations of
 // tests/_ftp_cloud_ref.py (cloud_from_geometry) from its undistort_points line to the end.  Reads f2, d, P, R1, R2, Ri and
@@ -96,16 +113,7 @@ __device__ __forceinline__ void ftp_triangulate(const FtpCloudGeom &G, double u,
     }
     const double Wp = (G.P[6] * a + G.P[7] * b) + G.P[8];
     const double hx = ((G.P[0] * a + G.P[1] * b) + G.P[2]) / Wp, hy = ((G.P[3] * a + G.P[4] * b) + G.P[5]) / Wp;
-    // the two rectifying homographies; of the projector point only x is used
-    const double ppx = ((G.R2[0] * hx + G.R2[1] * hy) + G.R2[2]) / ((G.R2[6] * hx + G.R2[7] * hy) + G.R2[8]);
-    const double Wc = (G.R1[6] * u + G.R1[7] * v) + G.R1[8];
-    const double pcx = ((G.R1[0] * u + G.R1[1] * v) + G.R1[2]) / Wc, pcy = ((G.R1[3] * u + G.R1[4] * v) + G.R1[5]) / Wc;
-    // disparity -> depth, common rotation undone
-    const double disparity = fabs(ppx - pcx);
-    const double px = G.baseline * (pcx / disparity), py = G.baseline * (pcy / disparity), pz = G.baseline * (1.0 / disparity);
-    o[0] = (G.Ri[0] * px + G.Ri[1] * py) + G.Ri[2] * pz;
-    o[1] = (G.Ri[3] * px + G.Ri[4] * py) + G.Ri[5] * pz;
-    o[2] = (G.Ri[6] * px + G.Ri[7] * py) + G.Ri[8] * pz;
+    rectified_triangulate(G, u, v, hx, hy, o);
 }
 
 // One pixel centre (u, v) and its unwrapped phase (already shifted by the fringe order) -> point o[0..2].

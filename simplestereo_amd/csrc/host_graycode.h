@@ -92,18 +92,20 @@ int graycode_cloud_launch(Ctx &c, const int32_t *d_decoded, long long npix, int 
 
 // Where the host forms keep things in the context's two staging buffers, each at a multiple of 256 bytes.  uwIn: the planes, mapx
 // and mapy of a checked stack S (host pointers); an absent input is 0 bytes of any address, and the buffer exists even without
-// planes (+ 1).  on_device: S with the staged pointers, the maps nullptr when absent.
+// planes (+ 1).  on_device: S with the staged pointers, the maps nullptr when absent.  A second stack (host_graycode_stereo.h)
+// starts at `base` = the first one's end().
 inline size_t gray_round(size_t b) { return (b + 255) & ~(size_t)255; }
 struct PlaneStaging {
     HostIn planes, mapx, mapy;
-    PlaneStaging(const PlaneStack &S, int n)
+    PlaneStaging(const PlaneStack &S, int n, size_t base = 0)
     {
         const size_t plane_bytes = (size_t)n * S.plane_stride, map_bytes = S.mapx ? (size_t)S.plane_stride * sizeof(float) : 0;
-        const size_t at_mapx = gray_round(plane_bytes + 1);
-        planes = HostIn{&Ctx::uwIn, plane_bytes ? (const void *)S.planes : this, plane_bytes, 0};
+        const size_t at_mapx = base + gray_round(plane_bytes + 1);
+        planes = HostIn{&Ctx::uwIn, plane_bytes ? (const void *)S.planes : this, plane_bytes, base};
         mapx = HostIn{&Ctx::uwIn, map_bytes ? (const void *)S.mapx : this, map_bytes, at_mapx};
         mapy = HostIn{&Ctx::uwIn, map_bytes ? (const void *)S.mapy : this, map_bytes, at_mapx + gray_round(map_bytes)};
     }
+    size_t end() const { return gray_round(mapy.at + mapy.bytes + 1); }
     PlaneStack on_device(Ctx &c, PlaneStack S) const
     {
         S.planes = (const uint8_t *)staged(c, &Ctx::uwIn, planes.at);

@@ -1,4 +1,4 @@
-// libssamd.so: host side of the C ABI declared in include/ssamd.h, include/ssamd_active.h, include/ssamd_graycode.h, include/ssamd_ftp_mapping.h and include/ssamd_structured_light.h (gfx950 / ROCm).
+// libssamd.so: host side of the C ABI declared in include/ssamd.h, include/ssamd_active.h, include/ssamd_graycode.h, include/ssamd_ftp_mapping.h, include/ssamd_structured_light.h and include/ssamd_graycode_stereo.h (gfx950 / ROCm).
 // Owns device scratch, chooses launch geometry, launches the HIP kernels.
 // There is deliberately no CPU code path for the operators of this library.
 // This file is the main translation unit and the map of the host side: the kernel headers, then the host sections (host_*.h), which it
@@ -25,6 +25,7 @@
 #include "../../include/ssamd_graycode.h"
 #include "../../include/ssamd_ftp_mapping.h"
 #include "../../include/ssamd_structured_light.h"
+#include "../../include/ssamd_graycode_stereo.h"
 #include "asw_shared.hip.h"
 #include "asw_kernels.hip.h"
 #include "asw_pipe_kernel.hip.h"
@@ -53,6 +54,7 @@ namespace ssamd {
 #include "graycode_kernels.hip.h"
 #include "ftp_mapping_kernels.hip.h"
 #include "phaseshift_kernels.hip.h"
+#include "graycode_stereo_kernels.hip.h"
 
 using namespace ssamd;
 
@@ -73,5 +75,6 @@ using namespace ssamd;
 #include "host_graycode.h"      // Gray-code decode, offsets and cloud (include/ssamd_graycode.h)
 #include "host_ftp_mapping.h"   // FTP carrier phase and per-pixel mapping cloud (include/ssamd_ftp_mapping.h)
 #include "host_phaseshift.h"    // phase-shift decode and the triangulation of correspondences (include/ssamd_structured_light.h)
+#include "host_graycode_stereo.h" // two-camera Gray code: scatter, match, cloud, point pairs (include/ssamd_graycode_stereo.h)
 #include "host_library.h"       // version, last error, device count, kernel names, options, counters, autotune switch, geometry queries, profile
 #include "host_debug.h"         // verification entry points (ssamd_bgr2lab, ssamd_debug_*) and debug_libm_kernel
